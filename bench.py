@@ -8,11 +8,20 @@ cut into a uniform 15x9 tile grid so that every CTU is an independent stream (on
 waves, when steps + warmup would not fit the run budget at that size; --frames to override); original planes are resident in HBM before the timed region.  With --gpus N every rank encodes its own
 frames per step (weak scaling, no data-path collective; frames are independent in All-Intra).
 
-Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel against HBM bandwidth with the
-algorithmic bytes of SURVEY.md §8d (49 152 B per 8-bit CTU) and adds the VALU issue fraction from the newest committed
-PMC summary (the kernel is instruction-issue bound, not HBM bound); `cpu_baseline` times the CPU oracle (a port of the
-reference path, oracle/) on a bounded sample of the same workload on this host and quotes the reference encoder's own
-measured rate (one core of the authoring container) beside it.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps and prints the headline figure with what
+the timed steps themselves yield: `roofline` prices the dominant kernel against HBM bandwidth with the algorithmic bytes
+of SURVEY.md §8d (49 152 B per 8-bit CTU), `work` carries the work counters of the last launch.
+
+`--full` adds everything that takes work of its own: the HBM traffic and the VALU issue fraction from the newest committed
+PMC summary (the kernel is instruction-issue bound, not HBM bound) and the layout variants quoted from profiles/, the loop
+filters (`deblock`, `sao_statistics`, `sao`, `alf`) on the pictures of the last step, and `cpu_baseline`, which times the CPU
+oracle (a port of the reference path, oracle/) on a bounded sample of the same workload on this host and quotes the reference
+encoder's own measured rate (one core of the authoring container) beside it.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/<name>.npy: the per-CTU results
+(`ctu_dist`, `ctu_frac_bits`, `ctu_cost`, `ctu_n_cu`: float64 [frames, CTUs]) and a fixed, seeded sample of the reconstructed
+planes (`reco_y`, `reco_cb`, `reco_cr`: float32; the sample positions depend on the batch's shape alone).  The pictures are
+seeded by their order count, so the same arguments give the same inputs in every run.
 
 `--gpus N` without a torchrun environment launches N ranks itself (before anything touches the GPU) and exits with
 their code.  With N > 1 every rank also emits its tiles' slice_data payloads and the final bitstream gather to rank 0
@@ -25,6 +34,8 @@ import os
 import sys
 import time
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -32,6 +43,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 B_CTU_8BIT = 49152          # 2 x 1.5 x 128 x 128 x 1 byte  
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: 8.0 TB/s spec
 
+
+DUMP_RECO_SAMPLES = 4 << 20   # --dump-outputs: reconstructed samples kept per component (3 x 4 Mi x 4 B = 48 MiB at most)
+DUMP_SEED = 20240521
 
 RUN_BUDGET_S = 380.0          # what all timed + warm-up steps of one run may take (auto batch size only)
 BUDGET_CTUS_PER_S = 150.0     # rate assumed for that (below the measured rate of the full tool set: 160-173 CTU/s in round 4)
@@ -111,6 +125,22 @@ def _cpu_job(job):
     return 0
 
 
+def dump_outputs(directory, res, frames):
+    """--dump-outputs: what compress_bound_frames handed its caller in the last timed step: the per-CTU results (whole) and the reconstructed planes the
+    call filled (a fixed, seeded sample of each component over all frames of the batch, in index order)"""
+    os.makedirs(directory, exist_ok=True)
+    for k in res.dtype.names:
+        np.save(os.path.join(directory, "ctu_%s.npy" % k), res[k].astype(np.float64))
+    rng = np.random.default_rng(DUMP_SEED)
+    for c, name in enumerate(("y", "cb", "cr")):
+        plane = np.stack([rec[c].cpu().numpy() for _, rec in frames]).ravel()
+        if plane.dtype == np.int16:                # 10-bit samples travel in 16-bit containers
+            plane = plane.view(np.uint16)
+        if plane.size > DUMP_RECO_SAMPLES:
+            plane = plane[np.sort(rng.integers(0, plane.size, DUMP_RECO_SAMPLES))]
+        np.save(os.path.join(directory, "reco_%s.npy" % name), plane.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -138,7 +168,11 @@ def main():
     ap.add_argument("--chroma-texture", type=float, default=0.5,
                     help="fraction of the luma texture mixed into the synthetic chroma planes (0 = smooth chroma)")
     ap.add_argument("--emit-payload", action="store_true", help="run the slice_data writer in the timed steps also at N = 1 (N > 1 always does: the job ends with the bitstream gather)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also: the PMC / layout figures quoted from profiles/, the loop filters on the pictures of the last step and the CPU baseline")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write what the last timed step returned (per-CTU results, a seeded sample of the reconstruction) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-sample-ctus", type=int, default=8)
     ap.add_argument("--cpu-procs", type=int, default=0, help="processes of the frame-parallel CPU baseline (0 = the host's usable cores, at most 16)")
     args = ap.parse_args()
@@ -151,7 +185,6 @@ def main():
                os.path.abspath(__file__)] + sys.argv[1:]
         sys.exit(subprocess.call(cmd))
 
-    import numpy as np
     import torch
     import torch.distributed as dist
 
@@ -231,6 +264,9 @@ def main():
     elapsed, outs = pkg.timed_steps(step, args.steps, args.warmup, world, device_sync=torch.cuda.synchronize, device="cuda")
     kernel_ms = [ms for _, ms in outs]
     counters = enc.counters()
+    if args.dump_outputs and rank == 0 and outs:
+        torch.cuda.synchronize()
+        dump_outputs(args.dump_outputs, outs[-1][0], frames)     # before anything below touches the reconstruction (the loop filters of --full work in place)
     gather = None
     if world > 1:
         # the final bitstream gather (north_star: RCCL over xGMI only here): payloads of this rank's frames -> rank 0, timed on its own
@@ -252,8 +288,8 @@ def main():
         achieved = ctus_per_step * b_ctu / avg_kernel_s / 1e9
         workload = ("%dx%d %d-bit 4:2:0 All-Intra QP%d full RDO, tools 0x%x%s, chroma texture %.2f, %d frame(s)/step/GPU, %dx%d uniform tiles = %d CTU streams per frame"
                     % (W, H, bd, args.qp, args.tools, (" (LMCS model on, limited-range luma)" if args.lmcs == "model" else " (LMCS model chosen by the picture analysis)") if lmcs else "", args.chroma_texture, args.frames, tc, tr, tc * tr))
-        traffic, traffic_src, traffic_split = pmc_traffic(workload)
-        valu = pmc_valu(workload)
+        traffic, traffic_src, traffic_split = pmc_traffic(workload) if args.full else (None, None, None)
+        valu = pmc_valu(workload) if args.full else None
         out = {
             "metric": "CTUs/sec (All-Intra, QP32)", "value": value, "unit": "CTU/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
@@ -278,7 +314,7 @@ def main():
             "roofline": {"bound": "hbm", "limiter": "not HBM: VALU issue and the serial chains of one CTU stream (mode controller, trellis, CABAC estimator); see valu.issue_frac and DESIGN.md", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                          "traffic": traffic, "traffic_split": traffic_split, "traffic_source": traffic_src, "kernel": ("vvcx_compress_wpp_kernel_" if args.wpp else "vvcx_compress_kernel_") + ("u8" if bd == 8 else "u16"), "kernel_ms": 1e3 * avg_kernel_s,
                          "algorithmic_bytes_per_launch": ctus_per_step * b_ctu, "valu": valu},
-            "variants": layout_variants(),
+            "variants": layout_variants() if args.full else {},
             "emit_payload": bool(emit),
             "work": {"satd_candidates_per_launch": int(counters[0]), "rd_tu_evaluations_per_launch": int(counters[1]),
                      "rd_pixels_per_launch": int(counters[2]), "nodes_per_launch": int(counters[3]),
@@ -292,6 +328,7 @@ def main():
             bps = 2 if bd == 10 else 1
             out["work"]["diagnostic_traffic_model_bytes_per_launch"] = float(counters[2]) * bps + float(counters[1]) * (4 * side + 1) * 2 + ctus_per_step * b_ctu
 
+    if rank == 0 and args.full:
         # secondary kernel (not part of the timed step): in-loop deblocking of the pictures just coded, an HBM-bound pass
         try:
             if lmcs:
@@ -376,6 +413,7 @@ def main():
                                                              "sample": "%d processes x the same %d-CTU sample, %.1f s wall incl. process start" % (nproc, nct, dtn)}
             except Exception as ex:
                 out["cpu_baseline"]["frame_parallel"] = {"error": str(ex)}
+    if rank == 0:
         if gather:
             out["gather"] = gather
         print(json.dumps(out))

@@ -7,15 +7,16 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
 def locked_make(directory, target):
-    """`make -s -C directory target` under a host-wide lock: the suite runs on several xdist workers (pytest.ini) and two of them must not rebuild the same library at once"""
+    """`make -s -C directory target` under a lock: the suite runs on several xdist workers (pytest.ini) and two of them must not rebuild the same library at once.
+    The lock is held on the build directory itself: nothing is written anywhere, and a lock file another user left behind cannot be in the way."""
     import fcntl
     import subprocess
-    with open("/tmp/vvcx_tests_make.lock", "w") as lk:
+    lk = os.open(directory, os.O_RDONLY)
+    try:
         fcntl.flock(lk, fcntl.LOCK_EX)
-        try:
-            subprocess.check_call(["make", "-s", "-C", directory, target])
-        finally:
-            fcntl.flock(lk, fcntl.LOCK_UN)
+        subprocess.check_call(["make", "-s", "-C", directory, target])
+    finally:
+        os.close(lk)                               # closing the descriptor drops the lock
 
 
 def pytest_configure(config):

@@ -761,7 +761,7 @@ def test_dct2_rows_sum_to_zero_except_the_dc_row():
 def test_resource_budget_of_the_compress_kernel(hip_lib):
     """The stream kernel is sized for five workgroups per CU (96 VGPRs, 32 KB LDS, 1280 resident streams per GPU).  A field too many in the LDS object
     drops the residency by one and makes the compiler give up the register target as well (seen in round 3: 41 008 B -> 257 VGPRs, one wave per SIMD), without any
-    test failing: check the built code object's metadata.  profiles/r04_codeobj.json is this report, written by __graft_entry__.build() and committed with the build it
+    test failing: check the built code object's metadata.  profiles/r04_codeobj.json is this report, written by tools/codeobj_report.py and committed with the build it
     describes: the test fails when the two disagree (a stale report was quoted for a round once)."""
     import importlib.util
     llvm = "/opt/rocm/lib/llvm/bin"
@@ -775,7 +775,7 @@ def test_resource_budget_of_the_compress_kernel(hip_lib):
         assert k["group_segment_fixed_size"] <= 32768, (name, k)                   # five workgroups per CU: 160 KB / 5
         assert k["vgpr_count"] + k.get("agpr_count", 0) <= 96, (name, k)           # five waves per SIMD: 512 / 5, allocation granule 8
     committed = json.load(open(os.path.join(ROOT, "profiles", "r04_codeobj.json")))
-    assert committed["kernels"] == r["kernels"], "profiles/r04_codeobj.json is not the report of the built libvvcx.so: run python tools/codeobj_report.py --out profiles/r04_codeobj.json (or __graft_entry__.build())"
+    assert committed["kernels"] == r["kernels"], "profiles/r04_codeobj.json is not the report of the built libvvcx.so: run python tools/codeobj_report.py --out profiles/r04_codeobj.json"
 
 
 def test_barrier_shape_of_the_operation_loop(hip_lib):
