@@ -301,7 +301,8 @@ int  vvcx_resident_streams(const vvcx_handle *h);
  * reference has its run-time seams — RdCost::m_afpDistortFunc[DF_*] (CL/RdCost.h:60,104) — and its CommonLib entry points
  * IntraPrediction::initIntraPatternChType + predIntraAng (CL/IntraPrediction.cpp:304,1064), BinProbModel_Std
  * (CL/Contexts.h:86-155), RdCost::calcRdCost (CL/RdCost.cpp:63), the scan tables (CL/Rom.cpp:133-370).  Test and
- * diagnostic entry points: all pointers are HOST memory, the work runs on the device the handle / call selects. */
+ * diagnostic entry points: all pointers are HOST memory, the work runs on the device the handle / call selects.  Like every entry point
+ * of this header they leave the calling thread's current HIP device as they found it (the LMCS analysis runs on that device). */
 /* SAD, SATD (RdCost::xGetHADs tiling and normalisation) and SSE of n pairs of w x h blocks stored back to back; out[n][3] */
 int  vvcx_distortion_batch(const int16_t *a, const int16_t *b, int w, int h, int n, uint64_t *out, int device);
 /* intra prediction of n blocks of one picture: reco = planar 4:2:0 samples of the handle's size and bit depth (uint8 / uint16),

@@ -11,9 +11,9 @@
 #include <limits>
 #include <algorithm>
 #include <vector>
-#include <algorithm>
 #include "vvcx.h"
 #include "vvcx_dev.h"
+#include "vvcx_host.h"        // DevBuf, ON_DEVICE / DevGuard, HIPCHK
 #include "vvcx_tables.h"      // host copy of the constant tables (context init values)
 
 extern "C" __global__ void vvcx_compress_kernel_u8(VxParams p);
@@ -55,20 +55,13 @@ extern "C" __global__ void vvcx_leaf_trq_kernel(const int16_t *org, int16_t *rec
 
 static thread_local char g_err[512];
 extern "C" const char *vvcx_last_error(void) { return g_err; }
-// (for the other translation units of the library: csrc/vvcx_lmcs.hip)
-extern "C" __attribute__((visibility("hidden"))) int vvcx_fail_msg_(int code, const char *msg) { snprintf(g_err, sizeof g_err, "%s", msg); return code; }
+// (for vvcx_host.h and the other translation units of the library: csrc/vvcx_lmcs.hip)
+extern "C" int vvcx_fail_msg_(int code, const char *msg) { snprintf(g_err, sizeof g_err, "%s", msg); return code; }
 static int fail(int code, const char *fmt, ...)
 {
   va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof g_err, fmt, ap); va_end(ap);
   return code;
 }
-// every entry point works on the handle's device and leaves the caller's current device as it found it
-struct DevGuard {
-  int prev; bool ok;
-  explicit DevGuard(int dev) : prev(-1), ok(false) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; ok = hipSetDevice(dev) == hipSuccess; }
-  ~DevGuard() { if (prev >= 0) (void) hipSetDevice(prev); }
-};
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(VVCX_ERR_DEVICE, "%s: %s", #x, hipGetErrorString(e_)); } while (0)
 
 struct vvcx_handle {
   vvcx_cfg cfg; vvcx_slice sl; bool have_slice;
@@ -82,29 +75,29 @@ struct vvcx_handle {
   int nsub;
   std::vector<int> ctu_sub, sub_tile, sub_above, tile_sub0, tile_nsub;      // sub-stream of each CTU; its tile; the sub-stream of the CTU row above in the same tile (-1: none); per tile: first sub-stream, count
   std::vector<std::vector<int>> sub_ctus;       // CTUs of each sub-stream in coding order
-  int32_t *train_rows_d; uint32_t *train_n_d; int train_cap;      // vvcx_enable_training_dump
-  int32_t *wpp_sched_d; int wpp_sched_cap; int wpp_rr;      // the launch's WPP scheduler state (vvcx_kernel.hip run_streams_wpp); test mode (env VVCX_WPP_TEST_INTERLEAVE)
-  int32_t *wpp_progress_d; uint16_t *wpp_sync_d;  // WPP: CTUs finished per (frame, sub-stream); the contexts behind the first CTU of each (m_entropyCodingSyncContextState)
+  DevBuf<int32_t> train_rows_d; DevBuf<uint32_t> train_n_d; int train_cap;      // vvcx_enable_training_dump: rows of 28 values, how many were asked for, room for train_cap rows
+  DevBuf<int32_t> wpp_sched_d; int wpp_rr;      // the launch's WPP scheduler state (vvcx_kernel.hip run_streams_wpp); test mode (env VVCX_WPP_TEST_INTERLEAVE)
+  DevBuf<int32_t> wpp_progress_d; DevBuf<uint16_t> wpp_sync_d;  // WPP: CTUs finished per (frame, sub-stream); the contexts behind the first CTU of each (m_entropyCodingSyncContextState)
   std::vector<int> next_idx;                    // per (frame, sub-stream): how many CTUs of the stream are done
-  // device memory
-  VxFrameDev *frames_d; int16_t *lev_d; VxUnit *units_d; uint16_t *stream_ctx_d;
-  uint8_t *scratch_d; size_t scratch_cap;
-  VxStreamDesc *streams_d; int32_t *task_ctu_d; VxCtuRes *results_d; int task_cap, stream_cap;
-  unsigned long long *counters_d;
+  // device memory: every *_d member owns its block (vvcx_host.h) and is freed with the handle
+  DevBuf<VxFrameDev> frames_d; DevBuf<int16_t> lev_d; DevBuf<VxUnit> units_d; DevBuf<uint16_t> stream_ctx_d;
+  DevBuf<uint8_t> scratch_d;
+  DevBuf<VxStreamDesc> streams_d; DevBuf<int32_t> task_ctu_d; DevBuf<VxCtuRes> results_d;
+  DevBuf<unsigned long long> counters_d;
   // optional slice_data writer: payload bytes per (frame, tile), byte ranges, persistent arithmetic-coder state
-  uint8_t *payload_d; uint64_t *payload_off_d; uint32_t *payload_cap_d; void *arith_d; std::vector<uint64_t> payload_off; std::vector<uint32_t> payload_cap;
+  DevBuf<uint8_t> payload_d; DevBuf<uint64_t> payload_off_d; DevBuf<uint32_t> payload_cap_d; DevBuf<uint8_t> arith_d; std::vector<uint64_t> payload_off; std::vector<uint32_t> payload_cap;
   // FAST_ALGORITHM forest (vvcx_set_forest)
-  VxForestNode *f_node_d; double *f_value_d; int32_t *f_root_d; int f_ntrees, f_nclasses; int32_t f_classes[8];
-  VxDqConst *dq_d;                              // dependent-quantiser constants per (chroma scale table, component, log2 w + log2 h)
+  DevBuf<VxForestNode> f_node_d; DevBuf<double> f_value_d; DevBuf<int32_t> f_root_d; int f_ntrees, f_nclasses; int32_t f_classes[8];
+  DevBuf<VxDqConst> dq_d;                           // dependent-quantiser constants per (chroma scale table, component, log2 w + log2 h)
   // LMCS of the current slice (vvcx_set_slice): LUTs and tables, their device copy (fwd | inv), the forward-mapped original luma of the bound pictures
   bool lmcs_on, lmcs_inverted; int16_t lmcs_fwd[1024], lmcs_inv[1024]; int32_t lmcs_pivot[17], lmcs_cadj[16];
-  int16_t *lmcs_lut_d; void *lmcs_org_d; size_t lmcs_org_cap;
+  DevBuf<int16_t> lmcs_lut_d; DevBuf<uint8_t> lmcs_org_d;
   std::vector<uint32_t> activity;               // per (frame, CTU) of the bound pictures: orders the stream queue of a launch, longest first
   hipEvent_t ev0, ev1; float last_ms, last_deblock_ms, last_sao_ms;
-  void *sao_tmp_d; size_t sao_tmp_cap; VxSaoEntry *sao_tab_d; size_t sao_tab_cap; uint8_t *sao_tile_d;      // vvcx_sao_bound_frames: picture copy, resolved parameters, CTU -> tile
-  uint8_t *db_edges_d; size_t db_edges_cap;      // vvcx_deblock_bound_frames: one edge byte per unit, map and direction
-  long long *sao_stat_d; size_t sao_stat_cap; float last_sao_stats_ms;      // vvcx_sao_statistics_bound_frames
-  VxAlfFrame *alf_tab_d; VxAlfCtu *alf_ctu_d; size_t alf_cap; float last_alf_ms;      // vvcx_alf_bound_frames: per-frame tables and per-CTU choices (the picture copy is the SAO one)
+  DevBuf<uint8_t> sao_tmp_d; DevBuf<VxSaoEntry> sao_tab_d; DevBuf<uint8_t> sao_tile_d;      // vvcx_sao_bound_frames: picture copy, resolved parameters, CTU -> tile
+  DevBuf<uint8_t> db_edges_d;      // vvcx_deblock_bound_frames: one edge byte per unit, map and direction
+  DevBuf<long long> sao_stat_d; float last_sao_stats_ms;      // vvcx_sao_statistics_bound_frames
+  DevBuf<VxAlfFrame> alf_tab_d; DevBuf<VxAlfCtu> alf_ctu_d; float last_alf_ms;      // vvcx_alf_bound_frames: per-frame tables and per-CTU choices (the picture copy is the SAO one)
   // a submitted, not yet collected launch (vvcx_submit_ctus .. vvcx_wait_ctus): staging the async copies read from / write to stays alive here
   bool pending; hipStream_t pend_stream; int pend_n; VxCtuRes *pend_res; int pend_cap;
   std::vector<VxStreamDesc> pend_sd; std::vector<int32_t> pend_task_ctu; std::vector<int> pend_src, pend_next; VxDqConst pend_dq[17 * 96];
@@ -169,8 +162,9 @@ extern "C" int vvcx_create(const vvcx_cfg *cfg, vvcx_handle **out)
   if ((cfg->pic_w & 7) || (cfg->pic_h & 7) || cfg->pic_w <= 0 || cfg->pic_h <= 0) return fail(VVCX_ERR_ARG, "picture size must be a positive multiple of 8");
   if (cfg->bit_depth != 8 && cfg->bit_depth != 10) return fail(VVCX_ERR_UNSUPPORTED, "bit depth %d", cfg->bit_depth);
   if (cfg->max_frames < 1 || cfg->tile_cols < 1 || cfg->tile_rows < 1) return fail(VVCX_ERR_ARG, "max_frames / tile grid");
-  vvcx_handle *h = new vvcx_handle();
-  h->cfg = *cfg; h->have_slice = false; h->n_frames = 0; h->last_ms = 0.f;
+  ON_DEVICE(cfg->device);
+  vvcx_handle *h = new vvcx_handle();          // every field zero, every buffer empty
+  h->cfg = *cfg;
   h->ctus_w = (cfg->pic_w + 127) >> 7; h->ctus_h = (cfg->pic_h + 127) >> 7;
   if (cfg->tile_cols > h->ctus_w || cfg->tile_rows > h->ctus_h) { delete h; return fail(VVCX_ERR_ARG, "more tiles than CTUs"); }
   h->uw = (cfg->pic_w + 3) >> 2; h->uh = (cfg->pic_h + 3) >> 2;
@@ -202,36 +196,27 @@ extern "C" int vvcx_create(const vvcx_cfg *cfg, vvcx_handle **out)
     }
     h->nsub = (int) h->sub_ctus.size();
   }
-  h->wpp_sched_d = nullptr; h->wpp_sched_cap = 0; { const char *e = getenv("VVCX_WPP_TEST_INTERLEAVE"); h->wpp_rr = e && *e == '1'; }
-  h->wpp_progress_d = nullptr; h->wpp_sync_d = nullptr; h->train_rows_d = nullptr; h->train_n_d = nullptr; h->train_cap = 0;
-  DevGuard guard(cfg->device);
-  if (!guard.ok) { delete h; return fail(VVCX_ERR_DEVICE, "hipSetDevice(%d) failed", cfg->device); }
+  { const char *e = getenv("VVCX_WPP_TEST_INTERLEAVE"); h->wpp_rr = e && *e == '1'; }
   const int wc = cfg->pic_w >> 1, hc = cfg->pic_h >> 1;
   h->lev_plane[0] = (size_t) cfg->pic_w * cfg->pic_h; h->lev_plane[1] = h->lev_plane[2] = (size_t) wc * hc;
   h->lev_frame = h->lev_plane[0] + 2 * h->lev_plane[1];
   h->units_plane = (size_t) h->uw * h->uh; h->units_frame = 2 * h->units_plane;
-  h->frames_d = nullptr; h->lev_d = nullptr; h->units_d = nullptr; h->stream_ctx_d = nullptr; h->scratch_d = nullptr; h->scratch_cap = 0;
-  h->payload_d = nullptr; h->payload_off_d = nullptr; h->payload_cap_d = nullptr; h->arith_d = nullptr;
-  h->streams_d = nullptr; h->task_ctu_d = nullptr; h->results_d = nullptr; h->task_cap = 0; h->stream_cap = 0; h->counters_d = nullptr;
-  h->sao_tmp_d = nullptr; h->sao_tmp_cap = 0; h->sao_tab_d = nullptr; h->sao_tab_cap = 0; h->sao_tile_d = nullptr; h->last_sao_ms = 0.f; h->alf_tab_d = nullptr; h->alf_ctu_d = nullptr; h->alf_cap = 0; h->last_alf_ms = 0.f; h->sao_stat_d = nullptr; h->sao_stat_cap = 0; h->last_sao_stats_ms = 0.f; h->db_edges_d = nullptr; h->db_edges_cap = 0;
-  h->dq_d = nullptr; h->lmcs_on = false; h->lmcs_inverted = false; h->lmcs_lut_d = nullptr; h->lmcs_org_d = nullptr; h->lmcs_org_cap = 0;
   const int F = cfg->max_frames;
-  if (hipMalloc((void **) &h->frames_d, sizeof(VxFrameDev) * F) != hipSuccess || hipMalloc((void **) &h->lev_d, h->lev_frame * 2 * F) != hipSuccess ||
-      hipMalloc((void **) &h->units_d, h->units_frame * sizeof(VxUnit) * F) != hipSuccess ||
-      hipMalloc((void **) &h->stream_ctx_d, (size_t) F * h->nsub * 2 * VXD_NUM_CTX * 2) != hipSuccess ||
-      ((cfg->tools & VVCX_TOOL_WPP) && (hipMalloc((void **) &h->wpp_progress_d, (size_t) F * h->nsub * 4) != hipSuccess || hipMalloc((void **) &h->wpp_sync_d, (size_t) F * h->nsub * 2 * VXD_NUM_CTX * 2) != hipSuccess)) ||
-      hipMalloc((void **) &h->counters_d, 56 * sizeof(unsigned long long)) != hipSuccess ||
-      hipMalloc((void **) &h->dq_d, 17 * 96 * sizeof(VxDqConst)) != hipSuccess) { vvcx_destroy(h); return fail(VVCX_ERR_DEVICE, "device allocation failed"); }
+  const size_t nstream = (size_t) F * h->nsub;
+  const bool wpp = (cfg->tools & VVCX_TOOL_WPP) != 0;
+  if (h->frames_d.alloc((size_t) F) != hipSuccess || h->lev_d.alloc(h->lev_frame * F) != hipSuccess || h->units_d.alloc(h->units_frame * F) != hipSuccess ||
+      h->stream_ctx_d.alloc(nstream * 2 * VXD_NUM_CTX) != hipSuccess ||
+      (wpp && (h->wpp_progress_d.alloc(nstream) != hipSuccess || h->wpp_sync_d.alloc(nstream * 2 * VXD_NUM_CTX) != hipSuccess)) ||
+      h->counters_d.alloc(56) != hipSuccess || h->dq_d.alloc(17 * 96) != hipSuccess) { vvcx_destroy(h); return fail(VVCX_ERR_DEVICE, "device allocation failed"); }
   if (cfg->emit_payload) {                       // VVCX_PAYLOAD_BYTES_PER_CTU per CTU: a CTU of 8-bit video at QP >= 17 stays far below (raw samples are 24 KB)
-    const size_t nstream = (size_t) F * h->nsub;
     h->payload_off.resize(nstream); h->payload_cap.resize(nstream);
     uint64_t off = 0;
     for (size_t s2 = 0; s2 < nstream; s2++) { const uint32_t cap = (uint32_t) h->sub_ctus[s2 % (size_t) h->nsub].size() * VVCX_PAYLOAD_BYTES_PER_CTU; h->payload_off[s2] = off; h->payload_cap[s2] = cap; off += cap; }
-    if (hipMalloc((void **) &h->payload_d, off) != hipSuccess || hipMalloc((void **) &h->payload_off_d, nstream * 8) != hipSuccess ||
-        hipMalloc((void **) &h->payload_cap_d, nstream * 4) != hipSuccess || hipMalloc(&h->arith_d, nstream * 32) != hipSuccess) { vvcx_destroy(h); return fail(VVCX_ERR_DEVICE, "device allocation failed"); }
-    (void) hipMemcpy(h->payload_off_d, h->payload_off.data(), nstream * 8, hipMemcpyHostToDevice);
-    (void) hipMemcpy(h->payload_cap_d, h->payload_cap.data(), nstream * 4, hipMemcpyHostToDevice);
-    (void) hipMemset(h->arith_d, 0, nstream * 32);
+    if (h->payload_d.alloc(off) != hipSuccess || h->payload_off_d.alloc(nstream) != hipSuccess || h->payload_cap_d.alloc(nstream) != hipSuccess ||
+        h->arith_d.alloc(nstream * 32) != hipSuccess) { vvcx_destroy(h); return fail(VVCX_ERR_DEVICE, "device allocation failed"); }
+    (void) hipMemcpy(h->payload_off_d.p, h->payload_off.data(), nstream * 8, hipMemcpyHostToDevice);
+    (void) hipMemcpy(h->payload_cap_d.p, h->payload_cap.data(), nstream * 4, hipMemcpyHostToDevice);
+    (void) hipMemset(h->arith_d.p, 0, nstream * 32);
   }
   (void) hipEventCreate(&h->ev0); (void) hipEventCreate(&h->ev1);
   *out = h;
@@ -241,15 +226,10 @@ extern "C" int vvcx_create(const vvcx_cfg *cfg, vvcx_handle **out)
 extern "C" void vvcx_destroy(vvcx_handle *h)
 {
   if (!h) return;
-  (void) hipFree(h->frames_d); (void) hipFree(h->lev_d); (void) hipFree(h->units_d); (void) hipFree(h->stream_ctx_d); (void) hipFree(h->scratch_d); (void) hipFree(h->wpp_progress_d); (void) hipFree(h->wpp_sync_d); (void) hipFree(h->wpp_sched_d); (void) hipFree(h->train_rows_d); (void) hipFree(h->train_n_d);
-  (void) hipFree(h->payload_d); (void) hipFree(h->payload_off_d); (void) hipFree(h->payload_cap_d); (void) hipFree(h->arith_d);
-  (void) hipFree(h->streams_d); (void) hipFree(h->task_ctu_d); (void) hipFree(h->results_d); (void) hipFree(h->counters_d);
-  (void) hipFree(h->sao_tmp_d); (void) hipFree(h->sao_tab_d); (void) hipFree(h->sao_tile_d); (void) hipFree(h->alf_tab_d); (void) hipFree(h->alf_ctu_d); (void) hipFree(h->sao_stat_d); (void) hipFree(h->db_edges_d);
-  (void) hipFree(h->f_node_d); (void) hipFree(h->f_value_d); (void) hipFree(h->f_root_d); (void) hipFree(h->dq_d); (void) hipFree(h->lmcs_lut_d); (void) hipFree(h->lmcs_org_d);
-  if (h->pending) (void) hipStreamSynchronize(h->pend_stream);
+  if (h->pending) (void) hipStreamSynchronize(h->pend_stream);      // first: a launch still in flight reads and writes what is freed below
   (void) hipHostFree(h->pend_res);
   (void) hipEventDestroy(h->ev0); (void) hipEventDestroy(h->ev1);
-  delete h;
+  delete h;                                     // frees every device buffer
 }
 
 // ---- slice-level inputs (host only)
@@ -313,14 +293,12 @@ extern "C" int vvcx_set_forest(vvcx_handle *h, int n_trees, int n_nodes, int n_c
   }
   for (int t = 0; t < n_trees; t++) if (root[t] < 0 || root[t] >= n_nodes) return fail(VVCX_ERR_ARG, "forest root %d out of range", t);
   for (int c = 0; c < n_classes; c++) if (classes[c] < 0 || classes[c] > 5) return fail(VVCX_ERR_ARG, "forest class label %d", classes[c]);
-  HIPCHK(hipSetDevice(h->cfg.device));
-  (void) hipFree(h->f_node_d); (void) hipFree(h->f_value_d); (void) hipFree(h->f_root_d); h->f_node_d = nullptr; h->f_value_d = nullptr; h->f_root_d = nullptr; h->f_ntrees = 0;
-  HIPCHK(hipMalloc((void **) &h->f_node_d, sizeof(VxForestNode) * (size_t) n_nodes));
-  HIPCHK(hipMalloc((void **) &h->f_value_d, sizeof(double) * (size_t) n_nodes * (size_t) n_classes));
-  HIPCHK(hipMalloc((void **) &h->f_root_d, sizeof(int32_t) * (size_t) n_trees));
-  HIPCHK(hipMemcpy(h->f_node_d, nodes.data(), sizeof(VxForestNode) * (size_t) n_nodes, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(h->f_value_d, value, sizeof(double) * (size_t) n_nodes * (size_t) n_classes, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(h->f_root_d, root, sizeof(int32_t) * (size_t) n_trees, hipMemcpyHostToDevice));
+  ON_DEVICE(h->cfg.device);
+  h->f_ntrees = 0; h->f_node_d.release(); h->f_value_d.release(); h->f_root_d.release();      // no forest until the new one is complete
+  HIPCHK(h->f_node_d.alloc((size_t) n_nodes)); HIPCHK(h->f_value_d.alloc((size_t) n_nodes * (size_t) n_classes)); HIPCHK(h->f_root_d.alloc((size_t) n_trees));
+  HIPCHK(hipMemcpy(h->f_node_d.p, nodes.data(), sizeof(VxForestNode) * (size_t) n_nodes, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->f_value_d.p, value, sizeof(double) * (size_t) n_nodes * (size_t) n_classes, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->f_root_d.p, root, sizeof(int32_t) * (size_t) n_trees, hipMemcpyHostToDevice));
   h->f_ntrees = n_trees; h->f_nclasses = n_classes;
   for (int c = 0; c < 8; c++) h->f_classes[c] = c < n_classes ? classes[c] : 0;
   return VVCX_OK;
@@ -407,7 +385,7 @@ extern "C" int vvcx_bind_frames(vvcx_handle *h, const vvcx_frame *frames, int n)
 {
   NOT_PENDING(h);
   if (!h || !frames) return fail(VVCX_ERR_ARG, "null argument");
-  DevGuard guard(h->cfg.device);
+  ON_DEVICE(h->cfg.device);
   if (n < 1 || n > h->cfg.max_frames) return fail(VVCX_ERR_ARG, "n_frames %d outside 1..%d", n, h->cfg.max_frames);
   if (!h->have_slice) return fail(VVCX_ERR_STATE, "vvcx_set_slice must precede vvcx_bind_frames");
   h->frames_h.resize((size_t) n);
@@ -420,10 +398,10 @@ extern "C" int vvcx_bind_frames(vvcx_handle *h, const vvcx_frame *frames, int n)
       const size_t bps = h->cfg.bit_depth == 8 ? 1 : 2;   // the deblocking kernel loads four samples at a time: strides and bases must keep that alignment
       if ((d.stride[c] & 3) || (((uintptr_t) d.org[c] | (uintptr_t) d.rec[c]) & (4 * bps - 1))) return fail(VVCX_ERR_ARG, "frame %d plane %d: base address / stride not aligned to 4 samples", f, c);
     }
-    int16_t *lev = h->lev_d + (size_t) f * h->lev_frame;
+    int16_t *lev = h->lev_d.p + (size_t) f * h->lev_frame;
     d.lev[0] = lev; d.lev[1] = lev + h->lev_plane[0]; d.lev[2] = lev + h->lev_plane[0] + h->lev_plane[1];
     d.lstride[0] = h->cfg.pic_w; d.lstride[1] = d.lstride[2] = h->cfg.pic_w >> 1;
-    d.units[0] = h->units_d + (size_t) f * h->units_frame; d.units[1] = d.units[0] + h->units_plane;
+    d.units[0] = h->units_d.p + (size_t) f * h->units_frame; d.units[1] = d.units[0] + h->units_plane;
   }
   h->lmcs_inverted = false;
   if (h->lmcs_on) {
@@ -432,48 +410,47 @@ extern "C" int vvcx_bind_frames(vvcx_handle *h, const vvcx_frame *frames, int n)
     const size_t bps = h->cfg.bit_depth == 8 ? 1 : 2;
     size_t need = 0;
     for (int f = 0; f < n; f++) need += (size_t) h->frames_h[(size_t) f].stride[0] * h->cfg.pic_h * bps;
-    if (need > h->lmcs_org_cap) { (void) hipFree(h->lmcs_org_d); h->lmcs_org_d = nullptr; h->lmcs_org_cap = 0; HIPCHK(hipMalloc(&h->lmcs_org_d, need)); h->lmcs_org_cap = need; }
-    if (!h->lmcs_lut_d) HIPCHK(hipMalloc((void **) &h->lmcs_lut_d, 2 * 1024 * 2));
-    HIPCHK(hipMemcpy(h->lmcs_lut_d, h->lmcs_fwd, 2048, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(h->lmcs_lut_d + 1024, h->lmcs_inv, 2048, hipMemcpyHostToDevice));
+    HIPCHK(h->lmcs_org_d.reserve(need));
+    HIPCHK(h->lmcs_lut_d.reserve(2 * 1024));
+    HIPCHK(hipMemcpy(h->lmcs_lut_d.p, h->lmcs_fwd, 2048, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(h->lmcs_lut_d.p + 1024, h->lmcs_inv, 2048, hipMemcpyHostToDevice));
     size_t off = 0;
     for (int f = 0; f < n; f++) {
       VxFrameDev &d = h->frames_h[(size_t) f];
-      void *dst = (uint8_t *) h->lmcs_org_d + off;
+      void *dst = h->lmcs_org_d.p + off;
       const unsigned blocks = (unsigned) (((size_t) h->cfg.pic_w * h->cfg.pic_h + VXD_NT - 1) / VXD_NT);
-      if (bps == 1) hipLaunchKernelGGL(vvcx_lmcs_map_kernel_u8, dim3(blocks), dim3(VXD_NT), 0, 0, (const uint8_t *) d.org[0], (uint8_t *) dst, h->cfg.pic_w, h->cfg.pic_h, d.stride[0], h->lmcs_lut_d);
-      else hipLaunchKernelGGL(vvcx_lmcs_map_kernel_u16, dim3(blocks), dim3(VXD_NT), 0, 0, (const uint16_t *) d.org[0], (uint16_t *) dst, h->cfg.pic_w, h->cfg.pic_h, d.stride[0], h->lmcs_lut_d);
+      if (bps == 1) hipLaunchKernelGGL(vvcx_lmcs_map_kernel_u8, dim3(blocks), dim3(VXD_NT), 0, 0, (const uint8_t *) d.org[0], (uint8_t *) dst, h->cfg.pic_w, h->cfg.pic_h, d.stride[0], h->lmcs_lut_d.p);
+      else hipLaunchKernelGGL(vvcx_lmcs_map_kernel_u16, dim3(blocks), dim3(VXD_NT), 0, 0, (const uint16_t *) d.org[0], (uint16_t *) dst, h->cfg.pic_w, h->cfg.pic_h, d.stride[0], h->lmcs_lut_d.p);
       HIPCHK(hipGetLastError());
       d.org[0] = dst;
       off += (size_t) d.stride[0] * h->cfg.pic_h * bps;
     }
   }
-  HIPCHK(hipMemcpy(h->frames_d, h->frames_h.data(), sizeof(VxFrameDev) * (size_t) n, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->frames_d.p, h->frames_h.data(), sizeof(VxFrameDev) * (size_t) n, hipMemcpyHostToDevice));
   if (h->cfg.tools & VVCX_TOOL_JCCR) {                    // the slice's joint_cb_cr_sign_flag from the bound picture (EL/EncSlice.cpp:1594-1597), left in its record
-    if (h->cfg.bit_depth == 8) hipLaunchKernelGGL(vvcx_jccr_sign_kernel_u8, dim3((unsigned) n), dim3(VXD_NT), 0, 0, h->frames_d, h->cfg.pic_w >> 1, h->cfg.pic_h >> 1);
-    else hipLaunchKernelGGL(vvcx_jccr_sign_kernel_u16, dim3((unsigned) n), dim3(VXD_NT), 0, 0, h->frames_d, h->cfg.pic_w >> 1, h->cfg.pic_h >> 1);
+    if (h->cfg.bit_depth == 8) hipLaunchKernelGGL(vvcx_jccr_sign_kernel_u8, dim3((unsigned) n), dim3(VXD_NT), 0, 0, h->frames_d.p, h->cfg.pic_w >> 1, h->cfg.pic_h >> 1);
+    else hipLaunchKernelGGL(vvcx_jccr_sign_kernel_u16, dim3((unsigned) n), dim3(VXD_NT), 0, 0, h->frames_d.p, h->cfg.pic_w >> 1, h->cfg.pic_h >> 1);
     HIPCHK(hipGetLastError());
   }
-  HIPCHK(hipMemset(h->units_d, 0, h->units_frame * sizeof(VxUnit) * (size_t) n));
-  HIPCHK(hipMemset(h->lev_d, 0, h->lev_frame * 2 * (size_t) n));
+  HIPCHK(hipMemset(h->units_d.p, 0, h->units_frame * sizeof(VxUnit) * (size_t) n));
+  HIPCHK(hipMemset(h->lev_d.p, 0, h->lev_frame * 2 * (size_t) n));
   std::vector<uint16_t> ctx((size_t) n * h->nsub * 2 * VXD_NUM_CTX);
   for (size_t s = 0; s < (size_t) n * h->nsub; s++) ctx_init_islice(h->sl.qp, &ctx[s * 2 * VXD_NUM_CTX], &ctx[s * 2 * VXD_NUM_CTX + VXD_NUM_CTX]);
-  HIPCHK(hipMemcpy(h->stream_ctx_d, ctx.data(), ctx.size() * 2, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->stream_ctx_d.p, ctx.data(), ctx.size() * 2, hipMemcpyHostToDevice));
   {
     // activity per CTU (read back here: binding is synchronous anyway); a failure only costs the ordering
     const size_t nact = (size_t) n * h->ctus_w * h->ctus_h;
     h->activity.assign(nact, 0);
-    unsigned *dact = nullptr;
-    if (hipMalloc((void **) &dact, nact * 4) == hipSuccess) {
+    DevBuf<unsigned> dact;
+    if (dact.alloc(nact) == hipSuccess) {
       const dim3 grid((unsigned) (h->ctus_w * h->ctus_h), (unsigned) n);
-      if (h->cfg.bit_depth == 8) hipLaunchKernelGGL(vvcx_ctu_activity_kernel_u8, grid, dim3(VXD_NT), 0, 0, h->frames_d, h->cfg.pic_w, h->cfg.pic_h, h->ctus_w, dact);
-      else hipLaunchKernelGGL(vvcx_ctu_activity_kernel_u16, grid, dim3(VXD_NT), 0, 0, h->frames_d, h->cfg.pic_w, h->cfg.pic_h, h->ctus_w, dact);
-      if (hipGetLastError() != hipSuccess || hipMemcpy(h->activity.data(), dact, nact * 4, hipMemcpyDeviceToHost) != hipSuccess) h->activity.assign(nact, 0);
-      (void) hipFree(dact);
+      if (h->cfg.bit_depth == 8) hipLaunchKernelGGL(vvcx_ctu_activity_kernel_u8, grid, dim3(VXD_NT), 0, 0, h->frames_d.p, h->cfg.pic_w, h->cfg.pic_h, h->ctus_w, dact.p);
+      else hipLaunchKernelGGL(vvcx_ctu_activity_kernel_u16, grid, dim3(VXD_NT), 0, 0, h->frames_d.p, h->cfg.pic_w, h->cfg.pic_h, h->ctus_w, dact.p);
+      if (hipGetLastError() != hipSuccess || hipMemcpy(h->activity.data(), dact.p, nact * 4, hipMemcpyDeviceToHost) != hipSuccess) h->activity.assign(nact, 0);
     }
   }
   h->n_frames = n;
-  if (h->wpp_progress_d) HIPCHK(hipMemset(h->wpp_progress_d, 0, (size_t) n * h->nsub * 4));
-  if (h->train_n_d) HIPCHK(hipMemset(h->train_n_d, 0, 4));
+  if (h->wpp_progress_d.p) HIPCHK(hipMemset(h->wpp_progress_d.p, 0, (size_t) n * h->nsub * 4));
+  if (h->train_n_d.p) HIPCHK(hipMemset(h->train_n_d.p, 0, 4));
   h->next_idx.assign((size_t) n * h->nsub, 0);
   return VVCX_OK;
 }
@@ -483,9 +460,9 @@ extern "C" int vvcx_ctus_per_frame(const vvcx_handle *h) { return h ? h->ctus_w 
 extern "C" int vvcx_resident_streams(const vvcx_handle *h)
 {
   if (!h) return 0;
-  DevGuard guard(h->cfg.device);
+  DevGuard guard(h->cfg.device);                  // (a count, not an error code: no ON_DEVICE)
   int cus = 0, per_cu = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->cfg.device) != hipSuccess) return 0;
+  if (!guard.ok || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->cfg.device) != hipSuccess) return 0;
   const bool wpp = (h->cfg.tools & VVCX_TOOL_WPP) != 0;
   const void *k = h->cfg.bit_depth == 8 ? (wpp ? (const void *) vvcx_compress_wpp_kernel_u8 : (const void *) vvcx_compress_kernel_u8) : (wpp ? (const void *) vvcx_compress_wpp_kernel_u16 : (const void *) vvcx_compress_kernel_u16);
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, VXD_NT, 0) != hipSuccess) return 0;
@@ -501,7 +478,7 @@ extern "C" int vvcx_submit_ctus(vvcx_handle *h, const vvcx_ctu_task *tasks, int 
   if (!h || (!tasks && n) || n < 0) return fail(VVCX_ERR_ARG, "bad argument");
   if (n == 0) { h->pending = true; h->pend_n = 0; h->pend_stream = (hipStream_t) hip_stream; h->pend_src.clear(); h->pend_next = h->next_idx; return VVCX_OK; }   // nothing to code: an empty submission, not an error
   if (h->n_frames == 0) return fail(VVCX_ERR_STATE, "no frames bound");
-  DevGuard guard(h->cfg.device);
+  ON_DEVICE(h->cfg.device);
   hipStream_t stream = (hipStream_t) hip_stream;
   const int nctu = h->ctus_w * h->ctus_h;
   // group tasks by stream, keeping their order; validate that every stream continues in tile raster order
@@ -555,30 +532,25 @@ extern "C" int vvcx_submit_ctus(vvcx_handle *h, const vvcx_ctu_task *tasks, int 
     sd.swap(sorted);
   }
   const int ns = (int) sd.size();
-  if (ns > h->stream_cap) { (void) hipFree(h->streams_d); h->streams_d = nullptr; HIPCHK(hipMalloc((void **) &h->streams_d, sizeof(VxStreamDesc) * (size_t) ns)); h->stream_cap = ns; }
-  if (n > h->task_cap) {
-    (void) hipFree(h->task_ctu_d); (void) hipFree(h->results_d); h->task_ctu_d = nullptr; h->results_d = nullptr;
-    HIPCHK(hipMalloc((void **) &h->task_ctu_d, sizeof(int32_t) * (size_t) n)); HIPCHK(hipMalloc((void **) &h->results_d, sizeof(VxCtuRes) * (size_t) n)); h->task_cap = n;
-  }
+  HIPCHK(h->streams_d.reserve((size_t) ns)); HIPCHK(h->task_ctu_d.reserve((size_t) n)); HIPCHK(h->results_d.reserve((size_t) n));
   const size_t per_stream = (h->cfg.tools & VVCX_TOOL_CU_REUSE) ? (size_t) VXD_SCRATCH_BYTES : (size_t) VXD_OFF_CACHE;   // the CU cache only when used
   // one workgroup per resident stream slot (they take the streams from a queue): scratch is per slot
   int resident = vvcx_resident_streams(h);
   if (resident < 1) resident = 1;
   const int grid = ns < resident ? ns : resident;
   const size_t need = (size_t) grid * per_stream;
-  if (need > h->scratch_cap) {
-    (void) hipFree(h->scratch_d); h->scratch_d = nullptr; HIPCHK(hipMalloc((void **) &h->scratch_d, need)); h->scratch_cap = need;
-    HIPCHK(hipMemsetAsync(h->scratch_d, 0, need, stream));       // CU-cache entries and generation counters start empty
-  }
+  bool grew;
+  HIPCHK(h->scratch_d.reserve(need, &grew));
+  if (grew) HIPCHK(hipMemsetAsync(h->scratch_d.p, 0, need, stream));       // CU-cache entries and generation counters start empty
   if (h->cfg.tools & VVCX_TOOL_WPP) {                    // scheduler state of this launch: nothing finished, nothing owned, every stream with its tasks left
-    if (4 + 2 * ns > h->wpp_sched_cap) { (void) hipFree(h->wpp_sched_d); h->wpp_sched_d = nullptr; HIPCHK(hipMalloc((void **) &h->wpp_sched_d, sizeof(int32_t) * (size_t) (4 + 2 * ns))); h->wpp_sched_cap = 4 + 2 * ns; }
+    HIPCHK(h->wpp_sched_d.reserve((size_t) (4 + 2 * ns)));
     std::vector<int32_t> sched((size_t) (4 + 2 * ns), 0);
     for (int i = 0; i < ns; i++) sched[(size_t) (4 + ns + i)] = sd[(size_t) i].n_tasks;
-    HIPCHK(hipMemcpy(h->wpp_sched_d, sched.data(), sched.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->wpp_sched_d.p, sched.data(), sched.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   }
-  HIPCHK(hipMemcpyAsync(h->streams_d, sd.data(), sizeof(VxStreamDesc) * (size_t) ns, hipMemcpyHostToDevice, stream));
-  HIPCHK(hipMemcpyAsync(h->task_ctu_d, task_ctu.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, stream));
-  HIPCHK(hipMemsetAsync(h->counters_d, 0, 56 * sizeof(unsigned long long), stream));
+  HIPCHK(hipMemcpyAsync(h->streams_d.p, sd.data(), sizeof(VxStreamDesc) * (size_t) ns, hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(h->task_ctu_d.p, task_ctu.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemsetAsync(h->counters_d.p, 0, 56 * sizeof(unsigned long long), stream));
 
   VxParams p; memset(&p, 0, sizeof p);
   p.pic_w = h->cfg.pic_w; p.pic_h = h->cfg.pic_h; p.bit_depth = h->cfg.bit_depth; p.chroma = h->cfg.chroma; p.tools = h->cfg.tools;
@@ -590,11 +562,11 @@ extern "C" int vvcx_submit_ctus(vvcx_handle *h, const vvcx_ctu_task *tasks, int 
     int qj = h->sl.qp_c[0] - 1; qj = qj < -bdo ? -bdo : qj > 63 ? 63 : qj; p.qp_tr_j = qj + bdo; }
   p.dist_scale = (double) (1 << 15) / h->sl.lambda;                       // CL/RdCost.cpp:79
   p.sqrt_lambda_fp = sqrt(h->sl.lambda) * (1.0 / (double) (1 << 15));     // EL/IntraSearch.cpp:297
-  p.frames = h->frames_d; p.streams = h->streams_d; p.task_ctu = h->task_ctu_d; p.results = h->results_d; p.stream_ctx = h->stream_ctx_d;
-  p.payload = h->payload_d; p.payload_off = h->payload_off_d; p.payload_cap = h->payload_cap_d; p.arith_state = h->arith_d;
-  p.scratch = h->scratch_d; p.scratch_per_stream = per_stream; p.counters = h->counters_d; p.ntiles = h->ntiles; p.nsub = h->nsub; p.wpp_progress = h->wpp_progress_d; p.wpp_sync = h->wpp_sync_d;
-  p.train_rows = h->train_rows_d; p.train_n = h->train_n_d; p.train_cap = h->train_cap; p.wpp_sched = h->wpp_sched_d; p.wpp_rr = h->wpp_rr;
-  p.f_node = h->f_node_d; p.f_value = h->f_value_d; p.f_root = h->f_root_d; p.f_ntrees = h->f_ntrees; p.f_nclasses = h->f_nclasses;
+  p.frames = h->frames_d.p; p.streams = h->streams_d.p; p.task_ctu = h->task_ctu_d.p; p.results = h->results_d.p; p.stream_ctx = h->stream_ctx_d.p;
+  p.payload = h->payload_d.p; p.payload_off = h->payload_off_d.p; p.payload_cap = h->payload_cap_d.p; p.arith_state = h->arith_d.p;
+  p.scratch = h->scratch_d.p; p.scratch_per_stream = per_stream; p.counters = h->counters_d.p; p.ntiles = h->ntiles; p.nsub = h->nsub; p.wpp_progress = h->wpp_progress_d.p; p.wpp_sync = h->wpp_sync_d.p;
+  p.train_rows = h->train_rows_d.p; p.train_n = h->train_n_d.p; p.train_cap = h->train_cap; p.wpp_sched = h->wpp_sched_d.p; p.wpp_rr = h->wpp_rr;
+  p.f_node = h->f_node_d.p; p.f_value = h->f_value_d.p; p.f_root = h->f_root_d.p; p.f_ntrees = h->f_ntrees; p.f_nclasses = h->f_nclasses;
   for (int c = 0; c < 8; c++) p.f_classes[c] = h->f_classes[c];
   p.n_streams = ns;
   p.lmcs_on = h->lmcs_on; p.lmcs_cadj_on = h->lmcs_on && h->sl.lmcs_chroma_adj; p.lmcs_min_bin = h->sl.lmcs_min_bin; p.lmcs_max_bin = h->sl.lmcs_max_bin;
@@ -635,8 +607,8 @@ extern "C" int vvcx_submit_ctus(vvcx_handle *h, const vvcx_ctu_task *tasks, int 
         }
       }
     }
-    HIPCHK(hipMemcpyAsync(h->dq_d, tab, sizeof h->pend_dq, hipMemcpyHostToDevice, stream));
-    p.dq_consts = h->dq_d;
+    HIPCHK(hipMemcpyAsync(h->dq_d.p, tab, sizeof h->pend_dq, hipMemcpyHostToDevice, stream));
+    p.dq_consts = h->dq_d.p;
   }
 
   HIPCHK(hipEventRecord(h->ev0, stream));
@@ -651,7 +623,7 @@ extern "C" int vvcx_submit_ctus(vvcx_handle *h, const vvcx_ctu_task *tasks, int 
     (void) hipHostFree(h->pend_res); h->pend_res = nullptr; h->pend_cap = 0;
     HIPCHK(hipHostMalloc((void **) &h->pend_res, sizeof(VxCtuRes) * (size_t) n, 0)); h->pend_cap = n;
   }
-  HIPCHK(hipMemcpyAsync(h->pend_res, h->results_d, sizeof(VxCtuRes) * (size_t) n, hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(h->pend_res, h->results_d.p, sizeof(VxCtuRes) * (size_t) n, hipMemcpyDeviceToHost, stream));
   h->pending = true; h->pend_stream = stream; h->pend_n = n;
   return VVCX_OK;
 }
@@ -662,7 +634,7 @@ extern "C" int vvcx_poll_ctus(vvcx_handle *h)
   if (!h) return fail(VVCX_ERR_ARG, "null handle");
   if (!h->pending) return fail(VVCX_ERR_STATE, "nothing submitted");
   if (h->pend_n == 0) return 1;
-  DevGuard guard(h->cfg.device);
+  ON_DEVICE(h->cfg.device);
   const hipError_t e = hipStreamQuery(h->pend_stream);
   if (e == hipSuccess) return 1;
   if (e == hipErrorNotReady) return 0;
@@ -677,12 +649,12 @@ extern "C" int vvcx_wait_ctus(vvcx_handle *h, vvcx_ctu_result *out, int n)
   if (n != h->pend_n || (!out && n)) return fail(VVCX_ERR_ARG, "vvcx_wait_ctus: %d results asked, %d tasks submitted", n, h->pend_n);
   h->pending = false;
   if (n == 0) return VVCX_OK;
-  DevGuard guard(h->cfg.device);
+  ON_DEVICE(h->cfg.device);
   HIPCHK(hipStreamSynchronize(h->pend_stream));
   HIPCHK(hipEventElapsedTime(&h->last_ms, h->ev0, h->ev1));
   if (h->cfg.tools & VVCX_TOOL_WPP) {
     int32_t st[2] = { 0, 0 };
-    HIPCHK(hipMemcpy(st, h->wpp_sched_d, sizeof st, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(st, h->wpp_sched_d.p, sizeof st, hipMemcpyDeviceToHost));
     if (st[1]) {
       // the rows' contexts, coder states and progress counts on the device have advanced part of the way; the host's positions have not: the streams cannot be continued
       h->n_frames = 0;
@@ -725,23 +697,31 @@ extern "C" int vvcx_compress_bound_frames(vvcx_handle *h, vvcx_ctu_result *out, 
   return VVCX_OK;
 }
 
+// what the picture-level passes behind the search (inverse LMCS, the loop filters) start from: every CTU of the bound pictures is coded
+static int require_all_coded(const vvcx_handle *h, const char *what)
+{
+  for (size_t i = 0; i < h->next_idx.size(); i++)
+    if (h->next_idx[i] != (int) h->sub_ctus[i % (size_t) h->nsub].size())
+      return fail(VVCX_ERR_STATE, "%s needs every CTU of the bound pictures coded (frame %d tile %d is not)", what, (int) (i / (size_t) h->nsub), h->sub_tile[i % (size_t) h->nsub]);
+  return VVCX_OK;
+}
+
 // LMCS: luma reconstruction of every bound picture back to the original domain, in place (the picture-level inverse rspSignal in front of the loop filters)
 extern "C" int vvcx_lmcs_inverse_reco(vvcx_handle *h, void *hip_stream)
 {
   NOT_PENDING(h);
   if (!h) return fail(VVCX_ERR_ARG, "null handle");
   if (!h->n_frames || !h->have_slice || !h->lmcs_on) return fail(VVCX_ERR_STATE, "no bound frames coded with an LMCS slice");
-  if (!h->lmcs_lut_d) return fail(VVCX_ERR_STATE, "the bound pictures were not prepared with an LMCS slice: vvcx_bind_frames after vvcx_set_slice");
+  if (!h->lmcs_lut_d.p) return fail(VVCX_ERR_STATE, "the bound pictures were not prepared with an LMCS slice: vvcx_bind_frames after vvcx_set_slice");
   if (h->lmcs_inverted) return fail(VVCX_ERR_STATE, "the reconstruction has already been mapped back");
-  for (size_t i = 0; i < h->next_idx.size(); i++)
-    if (h->next_idx[i] != (int) h->sub_ctus[i % (size_t) h->nsub].size()) return fail(VVCX_ERR_STATE, "every CTU of the bound pictures must be coded first (intra prediction reads mapped neighbours)");
-  HIPCHK(hipSetDevice(h->cfg.device));
+  if (const int rc = require_all_coded(h, "the inverse LMCS mapping (intra prediction reads mapped neighbours)")) return rc;
+  ON_DEVICE(h->cfg.device);
   hipStream_t stream = (hipStream_t) hip_stream;
   const unsigned blocks = (unsigned) (((size_t) h->cfg.pic_w * h->cfg.pic_h + VXD_NT - 1) / VXD_NT);
   for (int f = 0; f < h->n_frames; f++) {
     const VxFrameDev &d = h->frames_h[(size_t) f];
-    if (h->cfg.bit_depth == 8) hipLaunchKernelGGL(vvcx_lmcs_map_kernel_u8, dim3(blocks), dim3(VXD_NT), 0, stream, (const uint8_t *) d.rec[0], (uint8_t *) d.rec[0], h->cfg.pic_w, h->cfg.pic_h, d.stride[0], h->lmcs_lut_d + 1024);
-    else hipLaunchKernelGGL(vvcx_lmcs_map_kernel_u16, dim3(blocks), dim3(VXD_NT), 0, stream, (const uint16_t *) d.rec[0], (uint16_t *) d.rec[0], h->cfg.pic_w, h->cfg.pic_h, d.stride[0], h->lmcs_lut_d + 1024);
+    if (h->cfg.bit_depth == 8) hipLaunchKernelGGL(vvcx_lmcs_map_kernel_u8, dim3(blocks), dim3(VXD_NT), 0, stream, (const uint8_t *) d.rec[0], (uint8_t *) d.rec[0], h->cfg.pic_w, h->cfg.pic_h, d.stride[0], h->lmcs_lut_d.p + 1024);
+    else hipLaunchKernelGGL(vvcx_lmcs_map_kernel_u16, dim3(blocks), dim3(VXD_NT), 0, stream, (const uint16_t *) d.rec[0], (uint16_t *) d.rec[0], h->cfg.pic_w, h->cfg.pic_h, d.stride[0], h->lmcs_lut_d.p + 1024);
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipStreamSynchronize(stream));
@@ -756,19 +736,18 @@ extern "C" int vvcx_deblock_bound_frames(vvcx_handle *h, int beta_offset_div2, i
   NOT_PENDING(h);
   if (!h) return fail(VVCX_ERR_ARG, "null handle");
   if (!h->n_frames || !h->have_slice) return fail(VVCX_ERR_STATE, "no bound frames / slice");
-  for (size_t i = 0; i < h->next_idx.size(); i++)
-    if (h->next_idx[i] != (int) h->sub_ctus[i % (size_t) h->nsub].size()) return fail(VVCX_ERR_STATE, "deblocking needs every CTU of the bound pictures coded (frame %d tile %d is not)", (int) (i / (size_t) h->nsub), h->sub_tile[i % (size_t) h->nsub]);
+  if (const int rc = require_all_coded(h, "deblocking")) return rc;
   if (h->lmcs_on && !h->lmcs_inverted) return fail(VVCX_ERR_STATE, "LMCS slice: vvcx_lmcs_inverse_reco first (the loop filters work in the original domain)");
   if (beta_offset_div2 < -6 || beta_offset_div2 > 6 || tc_offset_div2 < -6 || tc_offset_div2 > 6) return fail(VVCX_ERR_ARG, "deblocking offsets outside -6..6");
-  HIPCHK(hipSetDevice(h->cfg.device));
+  ON_DEVICE(h->cfg.device);
   hipStream_t stream = (hipStream_t) hip_stream;
   VxDeblockParams p; memset(&p, 0, sizeof p);
-  p.frames = h->frames_d; p.uw = h->uw; p.uh = h->uh; p.bit_depth = h->cfg.bit_depth; p.chroma = h->cfg.chroma;
+  p.frames = h->frames_d.p; p.uw = h->uw; p.uh = h->uh; p.bit_depth = h->cfg.bit_depth; p.chroma = h->cfg.chroma;
   p.qp = h->sl.qp; p.qp_c[0] = h->sl.qp_c[0]; p.qp_c[1] = h->sl.qp_c[1]; p.beta_off2 = beta_offset_div2; p.tc_off2 = tc_offset_div2;
   const dim3 grid((unsigned) ((2 * h->uw * h->uh + 255) / 256), (unsigned) h->n_frames);
   const size_t nedge = (size_t) h->n_frames * 4 * h->uw * h->uh;
-  if (h->db_edges_cap < nedge) { (void) hipFree(h->db_edges_d); h->db_edges_d = nullptr; h->db_edges_cap = nedge; HIPCHK(hipMalloc((void **) &h->db_edges_d, nedge)); }
-  p.edges = h->db_edges_d;
+  HIPCHK(h->db_edges_d.reserve(nedge));
+  p.edges = h->db_edges_d.p;
   HIPCHK(hipEventRecord(h->ev0, stream));
   hipLaunchKernelGGL(vvcx_deblock_edges_kernel, grid, dim3(256), 0, stream, p);      // the unit records -> one edge byte per unit, map and direction
   HIPCHK(hipGetLastError());
@@ -784,6 +763,30 @@ extern "C" int vvcx_deblock_bound_frames(vvcx_handle *h, int beta_offset_div2, i
   return VVCX_OK;
 }
 extern "C" float vvcx_last_deblock_ms(const vvcx_handle *h) { return h ? h->last_deblock_ms : 0.f; }
+
+// One 4:2:0 picture of uint16 samples in host memory (stride = plane width) the way the picture-level leaf entries (vvcx_sao_picture, vvcx_alf_picture,
+// vvcx_deblock_cu_table) keep it on the device: the three planes in one allocation and the frame record the kernels reach them through; filtered in place, copied back
+struct DevPicture {
+  DevBuf<uint16_t> planes; DevBuf<VxFrameDev> frame; size_t ny, nc;
+  int upload(int pic_w, int pic_h, const uint16_t *y, const uint16_t *cb, const uint16_t *cr, VxUnit *units_d = nullptr)      // units_d: both trees' unit maps, for the deblocking
+  {
+    ny = (size_t) pic_w * pic_h; nc = ny >> 2;
+    HIPCHK(planes.alloc(ny + 2 * nc)); HIPCHK(frame.alloc(1));
+    VxFrameDev fd; memset(&fd, 0, sizeof fd);
+    fd.rec[0] = planes.p; fd.rec[1] = planes.p + ny; fd.rec[2] = planes.p + ny + nc; fd.stride[0] = pic_w; fd.stride[1] = fd.stride[2] = pic_w >> 1;
+    if (units_d) { fd.units[0] = units_d; fd.units[1] = units_d + (size_t) (pic_w >> 2) * (pic_h >> 2); }
+    HIPCHK(hipMemcpy(planes.p, y, ny * 2, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(planes.p + ny, cb, nc * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(planes.p + ny + nc, cr, nc * 2, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(frame.p, &fd, sizeof fd, hipMemcpyHostToDevice));
+    return VVCX_OK;
+  }
+  int download(uint16_t *y, uint16_t *cb, uint16_t *cr)      // behind the launches: their launch errors, their end, the planes
+  {
+    HIPCHK(hipGetLastError()); HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(y, planes.p, ny * 2, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(cb, planes.p + ny, nc * 2, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(cr, planes.p + ny + nc, nc * 2, hipMemcpyDeviceToHost));
+    return VVCX_OK;
+  }
+};
 
 // ≙ SampleAdaptiveOffset::SAOProcess (CL/SampleAdaptiveOffset.cpp:617-670) with the caller's parameters prm[frame][ctu][component]: merges are resolved here
 // (xReconstructBlkSAOParams 265-290: the CTU to the left / above in the same tile, in raster order; invertQuantOffsets 147-170), the samples are filtered on the device
@@ -830,23 +833,20 @@ extern "C" int vvcx_sao_bound_frames(vvcx_handle *h, const vvcx_sao_param *prm, 
   if (!h || !prm) return fail(VVCX_ERR_ARG, "null argument");
   if (!h->n_frames || !h->have_slice) return fail(VVCX_ERR_STATE, "no bound frames / slice");
   if (log2_offset_scale < 0 || log2_offset_scale > 4) return fail(VVCX_ERR_ARG, "log2 offset scale outside 0..4");
-  for (size_t i = 0; i < h->next_idx.size(); i++)
-    if (h->next_idx[i] != (int) h->sub_ctus[i % (size_t) h->nsub].size()) return fail(VVCX_ERR_STATE, "the loop filters need every CTU of the bound pictures coded");
+  if (const int rc = require_all_coded(h, "SAO")) return rc;
   if (h->lmcs_on && !h->lmcs_inverted) return fail(VVCX_ERR_STATE, "LMCS slice: vvcx_lmcs_inverse_reco first (the loop filters work in the original domain)");
   const int cw = h->ctus_w, chh = h->ctus_h, nctu = cw * chh;
   std::vector<VxSaoEntry> tab; std::vector<uint8_t> tile;
   const int rr = sao_resolve(prm, h->n_frames, cw, chh, h->cfg.tile_cols, h->cfg.tile_rows, log2_offset_scale, tab, tile);
   if (rr != VVCX_OK) return rr;
-  DevGuard guard(h->cfg.device);
+  ON_DEVICE(h->cfg.device);
   hipStream_t stream = (hipStream_t) hip_stream;
   const size_t bps = h->cfg.bit_depth == 8 ? 1 : 2, ny = (size_t) h->cfg.pic_w * h->cfg.pic_h, per_frame = ny + 2 * (ny >> 2);
-  if (h->sao_tmp_cap < (size_t) h->n_frames * per_frame * bps) { (void) hipFree(h->sao_tmp_d); h->sao_tmp_d = nullptr; h->sao_tmp_cap = (size_t) h->n_frames * per_frame * bps; HIPCHK(hipMalloc(&h->sao_tmp_d, h->sao_tmp_cap)); }
-  if (h->sao_tab_cap < tab.size()) { (void) hipFree(h->sao_tab_d); h->sao_tab_d = nullptr; h->sao_tab_cap = tab.size(); HIPCHK(hipMalloc((void **) &h->sao_tab_d, tab.size() * sizeof(VxSaoEntry))); }
-  if (!h->sao_tile_d) HIPCHK(hipMalloc((void **) &h->sao_tile_d, (size_t) nctu));
-  HIPCHK(hipMemcpyAsync(h->sao_tab_d, tab.data(), tab.size() * sizeof(VxSaoEntry), hipMemcpyHostToDevice, stream));
-  HIPCHK(hipMemcpyAsync(h->sao_tile_d, tile.data(), (size_t) nctu, hipMemcpyHostToDevice, stream));
+  HIPCHK(h->sao_tmp_d.reserve((size_t) h->n_frames * per_frame * bps)); HIPCHK(h->sao_tab_d.reserve(tab.size())); HIPCHK(h->sao_tile_d.reserve((size_t) nctu));
+  HIPCHK(hipMemcpyAsync(h->sao_tab_d.p, tab.data(), tab.size() * sizeof(VxSaoEntry), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(h->sao_tile_d.p, tile.data(), (size_t) nctu, hipMemcpyHostToDevice, stream));
   VxSaoParams p; memset(&p, 0, sizeof p);
-  p.frames = h->frames_d; p.table = h->sao_tab_d; p.tile_of_ctu = h->sao_tile_d; p.tmp = h->sao_tmp_d; p.tmp_frame = per_frame; p.tmp_comp[0] = 0; p.tmp_comp[1] = ny; p.tmp_comp[2] = ny + (ny >> 2);
+  p.frames = h->frames_d.p; p.table = h->sao_tab_d.p; p.tile_of_ctu = h->sao_tile_d.p; p.tmp = h->sao_tmp_d.p; p.tmp_frame = per_frame; p.tmp_comp[0] = 0; p.tmp_comp[1] = ny; p.tmp_comp[2] = ny + (ny >> 2);
   p.pic_w = h->cfg.pic_w; p.pic_h = h->cfg.pic_h; p.ctus_w = cw; p.ctus_h = chh; p.bit_depth = h->cfg.bit_depth; p.chroma = h->cfg.chroma; p.lf_across_tiles = lf_across_tiles != 0;
   HIPCHK(hipEventRecord(h->ev0, stream));
   sao_launch(p, h->n_frames, bps, stream);
@@ -868,31 +868,17 @@ extern "C" int vvcx_sao_picture(int pic_w, int pic_h, int bit_depth, int tile_co
   std::vector<VxSaoEntry> tab; std::vector<uint8_t> tile;
   const int rr = sao_resolve(prm, 1, cw, chh, tile_cols, tile_rows, log2_offset_scale, tab, tile);
   if (rr != VVCX_OK) return rr;
-  DevGuard guard(device);
-  const size_t ny = (size_t) pic_w * pic_h, nc = ny >> 2, per_frame = ny + 2 * nc;
-  uint16_t *pl_d = nullptr, *tmp_d = nullptr; VxFrameDev *fd_d = nullptr; VxSaoEntry *tab_d = nullptr; uint8_t *tile_d = nullptr;
-  int rc = VVCX_OK;
-  if (hipMalloc((void **) &pl_d, per_frame * 2) != hipSuccess || hipMalloc((void **) &tmp_d, per_frame * 2) != hipSuccess || hipMalloc((void **) &fd_d, sizeof(VxFrameDev)) != hipSuccess ||
-      hipMalloc((void **) &tab_d, tab.size() * sizeof(VxSaoEntry)) != hipSuccess || hipMalloc((void **) &tile_d, tile.size()) != hipSuccess)
-    rc = fail(VVCX_ERR_DEVICE, "hipMalloc failed for the SAO of a %dx%d picture", pic_w, pic_h);
-  if (rc == VVCX_OK) {
-    VxFrameDev fd; memset(&fd, 0, sizeof fd);
-    fd.rec[0] = pl_d; fd.rec[1] = pl_d + ny; fd.rec[2] = pl_d + ny + nc; fd.stride[0] = pic_w; fd.stride[1] = fd.stride[2] = pic_w >> 1;
-    VxSaoParams p; memset(&p, 0, sizeof p);
-    p.frames = fd_d; p.table = tab_d; p.tile_of_ctu = tile_d; p.tmp = tmp_d; p.tmp_frame = per_frame; p.tmp_comp[0] = 0; p.tmp_comp[1] = ny; p.tmp_comp[2] = ny + nc;
-    p.pic_w = pic_w; p.pic_h = pic_h; p.ctus_w = cw; p.ctus_h = chh; p.bit_depth = bit_depth; p.chroma = 1; p.lf_across_tiles = lf_across_tiles != 0;
-    bool ok = hipMemcpy(pl_d, y, ny * 2, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(pl_d + ny, cb, nc * 2, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(pl_d + ny + nc, cr, nc * 2, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(fd_d, &fd, sizeof fd, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(tab_d, tab.data(), tab.size() * sizeof(VxSaoEntry), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(tile_d, tile.data(), tile.size(), hipMemcpyHostToDevice) == hipSuccess;
-    if (ok) {
-      sao_launch(p, 1, 2, 0);
-      ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(y, pl_d, ny * 2, hipMemcpyDeviceToHost) == hipSuccess &&
-           hipMemcpy(cb, pl_d + ny, nc * 2, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(cr, pl_d + ny + nc, nc * 2, hipMemcpyDeviceToHost) == hipSuccess;
-    }
-    if (!ok) rc = fail(VVCX_ERR_DEVICE, "SAO of a picture: a HIP call failed");
-  }
-  (void) hipFree(pl_d); (void) hipFree(tmp_d); (void) hipFree(fd_d); (void) hipFree(tab_d); (void) hipFree(tile_d);
-  return rc;
+  ON_DEVICE(device);
+  DevPicture pic; DevBuf<uint16_t> tmp_d; DevBuf<VxSaoEntry> tab_d; DevBuf<uint8_t> tile_d;
+  if (const int rc = pic.upload(pic_w, pic_h, y, cb, cr)) return rc;
+  const size_t ny = pic.ny, nc = pic.nc, per_frame = ny + 2 * nc;
+  HIPCHK(tmp_d.alloc(per_frame)); HIPCHK(tab_d.alloc(tab.size())); HIPCHK(tile_d.alloc(tile.size()));
+  HIPCHK(hipMemcpy(tab_d.p, tab.data(), tab.size() * sizeof(VxSaoEntry), hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(tile_d.p, tile.data(), tile.size(), hipMemcpyHostToDevice));
+  VxSaoParams p; memset(&p, 0, sizeof p);
+  p.frames = pic.frame.p; p.table = tab_d.p; p.tile_of_ctu = tile_d.p; p.tmp = tmp_d.p; p.tmp_frame = per_frame; p.tmp_comp[0] = 0; p.tmp_comp[1] = ny; p.tmp_comp[2] = ny + nc;
+  p.pic_w = pic_w; p.pic_h = pic_h; p.ctus_w = cw; p.ctus_h = chh; p.bit_depth = bit_depth; p.chroma = 1; p.lf_across_tiles = lf_across_tiles != 0;
+  sao_launch(p, 1, 2, 0);
+  return pic.download(y, cb, cr);
 }
 extern "C" float vvcx_last_sao_ms(const vvcx_handle *h) { return h ? h->last_sao_ms : 0.f; }
 
@@ -903,8 +889,7 @@ extern "C" int vvcx_sao_statistics_bound_frames(vvcx_handle *h, int lf_across_ti
   NOT_PENDING(h);
   if (!h || !stats) return fail(VVCX_ERR_ARG, "null argument");
   if (!h->n_frames || !h->have_slice) return fail(VVCX_ERR_STATE, "no bound frames / slice");
-  for (size_t i = 0; i < h->next_idx.size(); i++)
-    if (h->next_idx[i] != (int) h->sub_ctus[i % (size_t) h->nsub].size()) return fail(VVCX_ERR_STATE, "the loop filters need every CTU of the bound pictures coded");
+  if (const int rc = require_all_coded(h, "the SAO statistics")) return rc;
   if (h->lmcs_on) return fail(VVCX_ERR_UNSUPPORTED, "SAO statistics of an LMCS slice: the handle keeps the mapped original only");
   const int cw = h->ctus_w, chh = h->ctus_h, nctu = cw * chh;
   std::vector<uint8_t> tile((size_t) nctu);
@@ -914,15 +899,14 @@ extern "C" int vvcx_sao_statistics_bound_frames(vvcx_handle *h, int lf_across_ti
     for (int i = 0; i < h->cfg.tile_rows; i++) if (a / cw >= (i * chh) / h->cfg.tile_rows) ty = i;
     tile[(size_t) a] = (uint8_t) (ty * h->cfg.tile_cols + tx);
   }
-  DevGuard guard(h->cfg.device);
+  ON_DEVICE(h->cfg.device);
   hipStream_t stream = (hipStream_t) hip_stream;
   const size_t n64 = (size_t) h->n_frames * nctu * 3 * 5 * 64;
-  if (h->sao_stat_cap < n64) { (void) hipFree(h->sao_stat_d); h->sao_stat_d = nullptr; h->sao_stat_cap = n64; HIPCHK(hipMalloc((void **) &h->sao_stat_d, n64 * sizeof(long long))); }
-  if (!h->sao_tile_d) HIPCHK(hipMalloc((void **) &h->sao_tile_d, (size_t) nctu));
-  HIPCHK(hipMemcpyAsync(h->sao_tile_d, tile.data(), (size_t) nctu, hipMemcpyHostToDevice, stream));
-  HIPCHK(hipMemsetAsync(h->sao_stat_d, 0, n64 * sizeof(long long), stream));
+  HIPCHK(h->sao_stat_d.reserve(n64)); HIPCHK(h->sao_tile_d.reserve((size_t) nctu));
+  HIPCHK(hipMemcpyAsync(h->sao_tile_d.p, tile.data(), (size_t) nctu, hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemsetAsync(h->sao_stat_d.p, 0, n64 * sizeof(long long), stream));
   VxSaoStatParams p; memset(&p, 0, sizeof p);
-  p.frames = h->frames_d; p.tile_of_ctu = h->sao_tile_d; p.out = h->sao_stat_d;
+  p.frames = h->frames_d.p; p.tile_of_ctu = h->sao_tile_d.p; p.out = h->sao_stat_d.p;
   p.pic_w = h->cfg.pic_w; p.pic_h = h->cfg.pic_h; p.ctus_w = cw; p.ctus_h = chh; p.bit_depth = h->cfg.bit_depth; p.chroma = h->cfg.chroma; p.lf_across_tiles = lf_across_tiles != 0;
   HIPCHK(hipEventRecord(h->ev0, stream));
   const dim3 grid((unsigned) nctu, 3u, (unsigned) h->n_frames);
@@ -930,7 +914,7 @@ extern "C" int vvcx_sao_statistics_bound_frames(vvcx_handle *h, int lf_across_ti
   else hipLaunchKernelGGL(vvcx_sao_stats_kernel_u16, grid, dim3(256), 0, stream, p);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(h->ev1, stream));
-  HIPCHK(hipMemcpyAsync(stats, h->sao_stat_d, n64 * sizeof(long long), hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipMemcpyAsync(stats, h->sao_stat_d.p, n64 * sizeof(long long), hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
   HIPCHK(hipEventElapsedTime(&h->last_sao_stats_ms, h->ev0, h->ev1));
   return VVCX_OK;
@@ -1230,26 +1214,22 @@ extern "C" int vvcx_alf_bound_frames(vvcx_handle *h, const vvcx_alf_aps *aps, in
   NOT_PENDING(h);
   if (!h || !slices || !ctus || (n_aps > 0 && !aps)) return fail(VVCX_ERR_ARG, "null argument");
   if (!h->n_frames || !h->have_slice) return fail(VVCX_ERR_STATE, "no bound frames / slice");
-  for (size_t i = 0; i < h->next_idx.size(); i++)
-    if (h->next_idx[i] != (int) h->sub_ctus[i % (size_t) h->nsub].size()) return fail(VVCX_ERR_STATE, "the loop filters need every CTU of the bound pictures coded");
+  if (const int rc = require_all_coded(h, "ALF")) return rc;
   if (h->lmcs_on && !h->lmcs_inverted) return fail(VVCX_ERR_STATE, "LMCS slice: vvcx_lmcs_inverse_reco first (the loop filters work in the original domain)");
   const int cw = h->ctus_w, chh = h->ctus_h, nctu = cw * chh;
   std::vector<VxAlfFrame> tabs; std::vector<VxAlfCtu> cts;
   const int rr = alf_build(aps, n_aps, slices, ctus, h->n_frames, nctu, h->cfg.bit_depth, h->cfg.chroma, tabs);
   if (rr != VVCX_OK) return rr;
   alf_ctus(slices, ctus, h->n_frames, nctu, h->cfg.chroma, cts);
-  DevGuard guard(h->cfg.device);
+  ON_DEVICE(h->cfg.device);
   hipStream_t stream = (hipStream_t) hip_stream;
   const size_t bps = h->cfg.bit_depth == 8 ? 1 : 2, ny = (size_t) h->cfg.pic_w * h->cfg.pic_h, per_frame = ny + 2 * (ny >> 2);
-  if (h->sao_tmp_cap < (size_t) h->n_frames * per_frame * bps) { (void) hipFree(h->sao_tmp_d); h->sao_tmp_d = nullptr; h->sao_tmp_cap = (size_t) h->n_frames * per_frame * bps; HIPCHK(hipMalloc(&h->sao_tmp_d, h->sao_tmp_cap)); }
-  if (h->alf_cap < (size_t) h->n_frames) {
-    (void) hipFree(h->alf_tab_d); (void) hipFree(h->alf_ctu_d); h->alf_tab_d = nullptr; h->alf_ctu_d = nullptr; h->alf_cap = (size_t) h->n_frames;
-    HIPCHK(hipMalloc((void **) &h->alf_tab_d, h->alf_cap * sizeof(VxAlfFrame))); HIPCHK(hipMalloc((void **) &h->alf_ctu_d, h->alf_cap * nctu * sizeof(VxAlfCtu)));
-  }
-  HIPCHK(hipMemcpyAsync(h->alf_tab_d, tabs.data(), tabs.size() * sizeof(VxAlfFrame), hipMemcpyHostToDevice, stream));
-  HIPCHK(hipMemcpyAsync(h->alf_ctu_d, cts.data(), cts.size() * sizeof(VxAlfCtu), hipMemcpyHostToDevice, stream));
+  HIPCHK(h->sao_tmp_d.reserve((size_t) h->n_frames * per_frame * bps));
+  HIPCHK(h->alf_tab_d.reserve((size_t) h->n_frames)); HIPCHK(h->alf_ctu_d.reserve((size_t) h->n_frames * nctu));
+  HIPCHK(hipMemcpyAsync(h->alf_tab_d.p, tabs.data(), tabs.size() * sizeof(VxAlfFrame), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(h->alf_ctu_d.p, cts.data(), cts.size() * sizeof(VxAlfCtu), hipMemcpyHostToDevice, stream));
   VxAlfParams p; memset(&p, 0, sizeof p);
-  p.frames = h->frames_d; p.tabs = h->alf_tab_d; p.ctus = h->alf_ctu_d; p.tmp = h->sao_tmp_d; p.tmp_frame = per_frame; p.tmp_comp[0] = 0; p.tmp_comp[1] = ny; p.tmp_comp[2] = ny + (ny >> 2);
+  p.frames = h->frames_d.p; p.tabs = h->alf_tab_d.p; p.ctus = h->alf_ctu_d.p; p.tmp = h->sao_tmp_d.p; p.tmp_frame = per_frame; p.tmp_comp[0] = 0; p.tmp_comp[1] = ny; p.tmp_comp[2] = ny + (ny >> 2);
   p.classes = nullptr; p.pic_w = h->cfg.pic_w; p.pic_h = h->cfg.pic_h; p.ctus_w = cw; p.ctus_h = chh; p.bit_depth = h->cfg.bit_depth; p.chroma = h->cfg.chroma;
   HIPCHK(hipEventRecord(h->ev0, stream));
   alf_launch(p, h->n_frames, bps, stream);
@@ -1270,33 +1250,20 @@ extern "C" int vvcx_alf_picture(int pic_w, int pic_h, int bit_depth, const vvcx_
   const int rr = alf_build(aps, n_aps, slice, ctus, 1, nctu, bit_depth, 1, tabs);
   if (rr != VVCX_OK) return rr;
   alf_ctus(slice, ctus, 1, nctu, 1, cts);
-  DevGuard guard(device);
-  const size_t ny = (size_t) pic_w * pic_h, nc = ny >> 2, per_frame = ny + 2 * nc, ncls = (size_t) (pic_w >> 2) * (pic_h >> 2);
-  uint16_t *pl_d = nullptr, *tmp_d = nullptr; VxFrameDev *fd_d = nullptr; VxAlfFrame *tab_d = nullptr; VxAlfCtu *ctu_d = nullptr; uint8_t *cls_d = nullptr;
-  int rc = VVCX_OK;
-  if (hipMalloc((void **) &pl_d, per_frame * 2) != hipSuccess || hipMalloc((void **) &tmp_d, per_frame * 2) != hipSuccess || hipMalloc((void **) &fd_d, sizeof(VxFrameDev)) != hipSuccess ||
-      hipMalloc((void **) &tab_d, sizeof(VxAlfFrame)) != hipSuccess || hipMalloc((void **) &ctu_d, cts.size() * sizeof(VxAlfCtu)) != hipSuccess || hipMalloc((void **) &cls_d, ncls) != hipSuccess)
-    rc = fail(VVCX_ERR_DEVICE, "hipMalloc failed for the ALF of a %dx%d picture", pic_w, pic_h);
-  if (rc == VVCX_OK) {
-    VxFrameDev fd; memset(&fd, 0, sizeof fd);
-    fd.rec[0] = pl_d; fd.rec[1] = pl_d + ny; fd.rec[2] = pl_d + ny + nc; fd.stride[0] = pic_w; fd.stride[1] = fd.stride[2] = pic_w >> 1;
-    VxAlfParams p; memset(&p, 0, sizeof p);
-    p.frames = fd_d; p.tabs = tab_d; p.ctus = ctu_d; p.tmp = tmp_d; p.tmp_frame = per_frame; p.tmp_comp[0] = 0; p.tmp_comp[1] = ny; p.tmp_comp[2] = ny + nc;
-    p.classes = cls_d; p.pic_w = pic_w; p.pic_h = pic_h; p.ctus_w = cw; p.ctus_h = chh; p.bit_depth = bit_depth; p.chroma = 1;
-    bool ok = hipMemcpy(pl_d, y, ny * 2, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(pl_d + ny, cb, nc * 2, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(pl_d + ny + nc, cr, nc * 2, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(fd_d, &fd, sizeof fd, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(tab_d, tabs.data(), sizeof(VxAlfFrame), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(ctu_d, cts.data(), cts.size() * sizeof(VxAlfCtu), hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemset(cls_d, 255, ncls) == hipSuccess;
-    if (ok) {
-      alf_launch(p, 1, 2, 0);
-      ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(y, pl_d, ny * 2, hipMemcpyDeviceToHost) == hipSuccess &&
-           hipMemcpy(cb, pl_d + ny, nc * 2, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(cr, pl_d + ny + nc, nc * 2, hipMemcpyDeviceToHost) == hipSuccess &&
-           (!classes || hipMemcpy(classes, cls_d, ncls, hipMemcpyDeviceToHost) == hipSuccess);
-    }
-    if (!ok) rc = fail(VVCX_ERR_DEVICE, "ALF of a picture: a HIP call failed");
-  }
-  (void) hipFree(pl_d); (void) hipFree(tmp_d); (void) hipFree(fd_d); (void) hipFree(tab_d); (void) hipFree(ctu_d); (void) hipFree(cls_d);
-  return rc;
+  ON_DEVICE(device);
+  DevPicture pic; DevBuf<uint16_t> tmp_d; DevBuf<VxAlfFrame> tab_d; DevBuf<VxAlfCtu> ctu_d; DevBuf<uint8_t> cls_d;
+  if (const int rc = pic.upload(pic_w, pic_h, y, cb, cr)) return rc;
+  const size_t ny = pic.ny, nc = pic.nc, per_frame = ny + 2 * nc, ncls = (size_t) (pic_w >> 2) * (pic_h >> 2);
+  HIPCHK(tmp_d.alloc(per_frame)); HIPCHK(tab_d.alloc(1)); HIPCHK(ctu_d.alloc(cts.size())); HIPCHK(cls_d.alloc(ncls));
+  HIPCHK(hipMemcpy(tab_d.p, tabs.data(), sizeof(VxAlfFrame), hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(ctu_d.p, cts.data(), cts.size() * sizeof(VxAlfCtu), hipMemcpyHostToDevice));
+  HIPCHK(hipMemset(cls_d.p, 255, ncls));
+  VxAlfParams p; memset(&p, 0, sizeof p);
+  p.frames = pic.frame.p; p.tabs = tab_d.p; p.ctus = ctu_d.p; p.tmp = tmp_d.p; p.tmp_frame = per_frame; p.tmp_comp[0] = 0; p.tmp_comp[1] = ny; p.tmp_comp[2] = ny + nc;
+  p.classes = cls_d.p; p.pic_w = pic_w; p.pic_h = pic_h; p.ctus_w = cw; p.ctus_h = chh; p.bit_depth = bit_depth; p.chroma = 1;
+  alf_launch(p, 1, 2, 0);
+  if (const int rc = pic.download(y, cb, cr)) return rc;
+  if (classes) HIPCHK(hipMemcpy(classes, cls_d.p, ncls, hipMemcpyDeviceToHost));
+  return VVCX_OK;
 }
 extern "C" float vvcx_last_alf_ms(const vvcx_handle *h) { return h ? h->last_alf_ms : 0.f; }
 
@@ -1326,37 +1293,22 @@ extern "C" int vvcx_deblock_cu_table(int pic_w, int pic_h, int bit_depth, int qp
     }
   }
   for (size_t i = 0; i < um.size(); i++) if (!um[i].tag) return fail(VVCX_ERR_ARG, "the CU table does not cover the picture (%s tree, 4x4 unit %d)", i < um.size() / 2 ? "luma" : "chroma", (int) (i % (um.size() / 2)));
-  DevGuard guard(device);
-  const size_t ny = (size_t) pic_w * pic_h, nc = ny >> 2;
-  VxUnit *um_d = nullptr; uint16_t *pl_d = nullptr; VxFrameDev *fd_d = nullptr; uint8_t *ed_d = nullptr;
-  int rc = VVCX_OK;
-  if (hipMalloc((void **) &ed_d, (size_t) 4 * uw * uh) != hipSuccess || hipMalloc((void **) &um_d, um.size() * sizeof(VxUnit)) != hipSuccess || hipMalloc((void **) &pl_d, (ny + 2 * nc) * 2) != hipSuccess || hipMalloc((void **) &fd_d, sizeof(VxFrameDev)) != hipSuccess)
-    rc = fail(VVCX_ERR_DEVICE, "hipMalloc failed for the deblocking of a %dx%d CU table", pic_w, pic_h);
-  if (rc == VVCX_OK) {
-    VxFrameDev fd; memset(&fd, 0, sizeof fd);
-    fd.rec[0] = pl_d; fd.rec[1] = pl_d + ny; fd.rec[2] = pl_d + ny + nc;
-    fd.stride[0] = pic_w; fd.stride[1] = fd.stride[2] = pic_w >> 1;
-    fd.units[0] = um_d; fd.units[1] = um_d + (size_t) uw * uh;
-    VxDeblockParams p; memset(&p, 0, sizeof p);
-    p.frames = fd_d; p.uw = uw; p.uh = uh; p.bit_depth = bit_depth; p.chroma = 1; p.qp = qp; p.qp_c[0] = qp_cb; p.qp_c[1] = qp_cr; p.beta_off2 = beta_offset_div2; p.tc_off2 = tc_offset_div2; p.edges = ed_d;
-    bool ok = hipMemcpy(um_d, um.data(), um.size() * sizeof(VxUnit), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(fd_d, &fd, sizeof fd, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(pl_d, y, ny * 2, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(pl_d + ny, cb, nc * 2, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(pl_d + ny + nc, cr, nc * 2, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok) { hipLaunchKernelGGL(vvcx_deblock_edges_kernel, dim3((unsigned) ((2 * uw * uh + 255) / 256), 1), dim3(256), 0, 0, p); ok = hipGetLastError() == hipSuccess; }
-    for (int dir = 0; dir < 2 && ok; dir++) {
-      p.dir = dir;
-      hipLaunchKernelGGL(vvcx_deblock_kernel_u16, dim3((unsigned) ((2 * uw * uh + 255) / 256), 1), dim3(256), 0, 0, p);
-      ok = hipGetLastError() == hipSuccess;
-    }
-    ok = ok && hipDeviceSynchronize() == hipSuccess && hipMemcpy(y, pl_d, ny * 2, hipMemcpyDeviceToHost) == hipSuccess && hipMemcpy(cb, pl_d + ny, nc * 2, hipMemcpyDeviceToHost) == hipSuccess &&
-         hipMemcpy(cr, pl_d + ny + nc, nc * 2, hipMemcpyDeviceToHost) == hipSuccess;
-    if (!ok) rc = fail(VVCX_ERR_DEVICE, "deblocking of a CU table: a HIP call failed");
+  ON_DEVICE(device);
+  DevPicture pic; DevBuf<VxUnit> um_d; DevBuf<uint8_t> ed_d;
+  HIPCHK(ed_d.alloc((size_t) 4 * uw * uh)); HIPCHK(um_d.alloc(um.size()));
+  HIPCHK(hipMemcpy(um_d.p, um.data(), um.size() * sizeof(VxUnit), hipMemcpyHostToDevice));
+  if (const int rc = pic.upload(pic_w, pic_h, y, cb, cr, um_d.p)) return rc;
+  VxDeblockParams p; memset(&p, 0, sizeof p);
+  p.frames = pic.frame.p; p.uw = uw; p.uh = uh; p.bit_depth = bit_depth; p.chroma = 1; p.qp = qp; p.qp_c[0] = qp_cb; p.qp_c[1] = qp_cr; p.beta_off2 = beta_offset_div2; p.tc_off2 = tc_offset_div2; p.edges = ed_d.p;
+  const dim3 grid((unsigned) ((2 * uw * uh + 255) / 256), 1);
+  hipLaunchKernelGGL(vvcx_deblock_edges_kernel, grid, dim3(256), 0, 0, p);
+  HIPCHK(hipGetLastError());
+  for (int dir = 0; dir < 2; dir++) {
+    p.dir = dir;
+    hipLaunchKernelGGL(vvcx_deblock_kernel_u16, grid, dim3(256), 0, 0, p);
+    HIPCHK(hipGetLastError());
   }
-  if (ed_d) (void) hipFree(ed_d);
-  if (um_d) (void) hipFree(um_d);
-  if (pl_d) (void) hipFree(pl_d);
-  if (fd_d) (void) hipFree(fd_d);
-  return rc;
+  return pic.download(y, cb, cr);
 }
 
 // quantised levels of one component of a coded picture at their sample positions (≙ tu.getCoeffs(compID) of the final TUs), host plane
@@ -1366,8 +1318,8 @@ extern "C" int vvcx_get_levels(vvcx_handle *h, int frame, int comp, int16_t *pla
   if (!h || !plane || frame < 0 || frame >= h->n_frames || comp < 0 || comp > 2) return fail(VVCX_ERR_ARG, "bad argument");
   const int w = comp ? h->cfg.pic_w >> 1 : h->cfg.pic_w, hh = comp ? h->cfg.pic_h >> 1 : h->cfg.pic_h;
   if (stride < w) return fail(VVCX_ERR_ARG, "stride smaller than the plane width");
-  HIPCHK(hipSetDevice(h->cfg.device));
-  const int16_t *src = h->lev_d + (size_t) frame * h->lev_frame + (comp == 0 ? 0 : comp == 1 ? h->lev_plane[0] : h->lev_plane[0] + h->lev_plane[1]);
+  ON_DEVICE(h->cfg.device);
+  const int16_t *src = h->lev_d.p + (size_t) frame * h->lev_frame + (comp == 0 ? 0 : comp == 1 ? h->lev_plane[0] : h->lev_plane[0] + h->lev_plane[1]);
   std::vector<int16_t> tmp((size_t) w * hh);
   HIPCHK(hipMemcpy(tmp.data(), src, tmp.size() * 2, hipMemcpyDeviceToHost));
   for (int y = 0; y < hh; y++) memcpy(plane + (size_t) y * stride, tmp.data() + (size_t) y * w, (size_t) w * 2);
@@ -1378,9 +1330,9 @@ extern "C" int vvcx_get_cus(vvcx_handle *h, int frame, vvcx_cu *cus, int max_cus
 {
   NOT_PENDING(h);
   if (!h || !n_cus || frame < 0 || frame >= h->n_frames) return fail(VVCX_ERR_ARG, "bad argument");
-  DevGuard guard(h->cfg.device);
+  ON_DEVICE(h->cfg.device);
   std::vector<VxUnit> um(h->units_frame);
-  HIPCHK(hipMemcpy(um.data(), h->units_d + (size_t) frame * h->units_frame, h->units_frame * sizeof(VxUnit), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(um.data(), h->units_d.p + (size_t) frame * h->units_frame, h->units_frame * sizeof(VxUnit), hipMemcpyDeviceToHost));
   int n = 0;
   for (int ry = 0; ry < h->ctus_h; ry++) for (int rx = 0; rx < h->ctus_w; rx++)
     for (int ch = 0; ch < (h->cfg.chroma ? 2 : 1); ch++) {
@@ -1454,9 +1406,9 @@ extern "C" int vvcx_get_counters(vvcx_handle *h, uint64_t out[4])
 {
   NOT_PENDING(h);
   if (!h || !out) return fail(VVCX_ERR_ARG, "null argument");
-  DevGuard guard(h->cfg.device);
+  ON_DEVICE(h->cfg.device);
   unsigned long long c[4];
-  HIPCHK(hipMemcpy(c, h->counters_d, sizeof c, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(c, h->counters_d.p, sizeof c, hipMemcpyDeviceToHost));
   for (int i = 0; i < 4; i++) out[i] = c[i];
   return VVCX_OK;
 }
@@ -1467,9 +1419,9 @@ extern "C" int vvcx_get_profile(vvcx_handle *h, uint64_t out[48])
 {
   NOT_PENDING(h);
   if (!h || !out) return fail(VVCX_ERR_ARG, "null argument");
-  DevGuard guard(h->cfg.device);
+  ON_DEVICE(h->cfg.device);
   unsigned long long c[52];
-  HIPCHK(hipMemcpy(c, h->counters_d, sizeof c, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(c, h->counters_d.p, sizeof c, hipMemcpyDeviceToHost));
   for (int i = 0; i < 48; i++) out[i] = c[4 + i];
   return VVCX_OK;
 }
@@ -1477,12 +1429,6 @@ extern "C" int vvcx_get_profile(vvcx_handle *h, uint64_t out[48])
 
 // ------------------------------------------------------------------------------------------------ leaf operators
 namespace {
-struct DevBuf {                         // device allocation released on scope exit
-  void *p = nullptr;
-  ~DevBuf() { if (p) (void) hipFree(p); }
-  hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
-  template <typename T> T *as() { return (T *) p; }
-};
 bool pow2_block(int w, int h) { return w >= 2 && h >= 2 && w <= 64 && h <= 64 && !(w & (w - 1)) && !(h & (h - 1)); }
 }
 
@@ -1490,12 +1436,12 @@ extern "C" int vvcx_distortion_batch(const int16_t *a, const int16_t *b, int w, 
 {
   if (!a || !b || !out || n < 0 || !pow2_block(w, h)) return fail(VVCX_ERR_ARG, "bad argument");
   if (n == 0) return VVCX_OK;
-  HIPCHK(hipSetDevice(device));
+  ON_DEVICE(device);
   const size_t bytes = (size_t) n * w * h * 2;
-  DevBuf da, db, ds, dout;
-  HIPCHK(da.alloc(bytes)); HIPCHK(db.alloc(bytes)); HIPCHK(ds.alloc(bytes)); HIPCHK(dout.alloc((size_t) n * 3 * 8));
+  DevBuf<int16_t> da, db, ds; DevBuf<unsigned long long> dout;
+  HIPCHK(da.alloc(bytes / 2)); HIPCHK(db.alloc(bytes / 2)); HIPCHK(ds.alloc(bytes / 2)); HIPCHK(dout.alloc((size_t) n * 3));
   HIPCHK(hipMemcpy(da.p, a, bytes, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(db.p, b, bytes, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(vvcx_leaf_dist_kernel, dim3((unsigned) n), dim3(VXD_NT), 0, 0, da.as<int16_t>(), db.as<int16_t>(), w, h, ds.as<int16_t>(), dout.as<unsigned long long>());
+  hipLaunchKernelGGL(vvcx_leaf_dist_kernel, dim3((unsigned) n), dim3(VXD_NT), 0, 0, da.p, db.p, w, h, ds.p, dout.p);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpy(out, dout.p, (size_t) n * 3 * 8, hipMemcpyDeviceToHost));
   return VVCX_OK;
@@ -1506,7 +1452,7 @@ extern "C" int vvcx_intra_pred_batch(vvcx_handle *h, const void *const reco[3], 
   NOT_PENDING(h);
   if (!h || !reco || !coded || !cases || !pred || n < 0) return fail(VVCX_ERR_ARG, "bad argument");
   if (n == 0) return VVCX_OK;
-  HIPCHK(hipSetDevice(h->cfg.device));
+  ON_DEVICE(h->cfg.device);
   const int bps = h->cfg.bit_depth == 8 ? 1 : 2, W = h->cfg.pic_w, H = h->cfg.pic_h;
   std::vector<int> off((size_t) n); size_t total = 0;
   for (int i = 0; i < n; i++) {
@@ -1516,7 +1462,7 @@ extern "C" int vvcx_intra_pred_batch(vvcx_handle *h, const void *const reco[3], 
         (c.mrl != 0 && (c.comp != 0 || (c.mrl != 1 && c.mrl != 3)))) return fail(VVCX_ERR_ARG, "bad prediction case %d", i);
     off[(size_t) i] = (int) total; total += (size_t) c.w * c.h;
   }
-  DevBuf dplane[3], dunits, dframe, dcases, doff, dpred;
+  DevBuf<uint8_t> dplane[3]; DevBuf<VxUnit> dunits; DevBuf<VxFrameDev> dframe; DevBuf<VxLeafPred> dcases; DevBuf<int> doff; DevBuf<int16_t> dpred;
   VxFrameDev fd; memset(&fd, 0, sizeof fd);
   for (int c = 0; c < 3; c++) {
     const size_t pw = c ? W >> 1 : W, ph = c ? H >> 1 : H;
@@ -1527,16 +1473,16 @@ extern "C" int vvcx_intra_pred_batch(vvcx_handle *h, const void *const reco[3], 
   const size_t nu = (size_t) h->uw * h->uh;
   std::vector<VxUnit> units(2 * nu); memset(units.data(), 0, units.size() * sizeof(VxUnit));
   for (int t = 0; t < 2; t++) { if (!coded[t]) return fail(VVCX_ERR_ARG, "coded map %d is null", t); for (size_t i = 0; i < nu; i++) units[(size_t) t * nu + i].tag = coded[t][i] ? 1 : 0; }
-  HIPCHK(dunits.alloc(units.size() * sizeof(VxUnit))); HIPCHK(hipMemcpy(dunits.p, units.data(), units.size() * sizeof(VxUnit), hipMemcpyHostToDevice));
-  fd.units[0] = dunits.as<VxUnit>(); fd.units[1] = dunits.as<VxUnit>() + nu;
-  HIPCHK(dframe.alloc(sizeof fd)); HIPCHK(hipMemcpy(dframe.p, &fd, sizeof fd, hipMemcpyHostToDevice));
-  HIPCHK(dcases.alloc((size_t) n * sizeof(VxLeafPred))); HIPCHK(hipMemcpy(dcases.p, cases, (size_t) n * sizeof(VxLeafPred), hipMemcpyHostToDevice));
-  HIPCHK(doff.alloc((size_t) n * 4)); HIPCHK(hipMemcpy(doff.p, off.data(), (size_t) n * 4, hipMemcpyHostToDevice));
-  HIPCHK(dpred.alloc(total * 2));
+  HIPCHK(dunits.alloc(units.size())); HIPCHK(hipMemcpy(dunits.p, units.data(), units.size() * sizeof(VxUnit), hipMemcpyHostToDevice));
+  fd.units[0] = dunits.p; fd.units[1] = dunits.p + nu;
+  HIPCHK(dframe.alloc(1)); HIPCHK(hipMemcpy(dframe.p, &fd, sizeof fd, hipMemcpyHostToDevice));
+  HIPCHK(dcases.alloc((size_t) n)); HIPCHK(hipMemcpy(dcases.p, cases, (size_t) n * sizeof(VxLeafPred), hipMemcpyHostToDevice));
+  HIPCHK(doff.alloc((size_t) n)); HIPCHK(hipMemcpy(doff.p, off.data(), (size_t) n * 4, hipMemcpyHostToDevice));
+  HIPCHK(dpred.alloc(total));
   VxParams p; memset(&p, 0, sizeof p);
-  p.pic_w = W; p.pic_h = H; p.bit_depth = h->cfg.bit_depth; p.tools = h->cfg.tools; p.uw = h->uw; p.uh = h->uh; p.frames = dframe.as<VxFrameDev>();
-  if (bps == 1) hipLaunchKernelGGL(vvcx_leaf_pred_kernel_u8, dim3((unsigned) n), dim3(VXD_NT), 0, 0, p, dcases.as<VxLeafPred>(), dpred.as<int16_t>(), doff.as<int>());
-  else hipLaunchKernelGGL(vvcx_leaf_pred_kernel_u16, dim3((unsigned) n), dim3(VXD_NT), 0, 0, p, dcases.as<VxLeafPred>(), dpred.as<int16_t>(), doff.as<int>());
+  p.pic_w = W; p.pic_h = H; p.bit_depth = h->cfg.bit_depth; p.tools = h->cfg.tools; p.uw = h->uw; p.uh = h->uh; p.frames = dframe.p;
+  if (bps == 1) hipLaunchKernelGGL(vvcx_leaf_pred_kernel_u8, dim3((unsigned) n), dim3(VXD_NT), 0, 0, p, dcases.p, dpred.p, doff.p);
+  else hipLaunchKernelGGL(vvcx_leaf_pred_kernel_u16, dim3((unsigned) n), dim3(VXD_NT), 0, 0, p, dcases.p, dpred.p, doff.p);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpy(pred, dpred.p, total * 2, hipMemcpyDeviceToHost));
   return VVCX_OK;
@@ -1562,12 +1508,12 @@ extern "C" int vvcx_ctx_init(int qp, uint16_t *s0, uint16_t *s1)
 extern "C" int vvcx_cabac_code_bins(uint16_t *s0, uint16_t *s1, int ctx, const uint8_t *bins, int nbins, uint64_t *frac_bits, int device)
 {
   if (!s0 || !s1 || !bins || !frac_bits || nbins < 0 || ctx < 0 || ctx >= VX_NUM_CTX_REF) return fail(VVCX_ERR_ARG, "bad argument");      // ctx: the reference's flat index; only its adaptation rate matters
-  HIPCHK(hipSetDevice(device));
-  DevBuf dio, dbins, dbits;
+  ON_DEVICE(device);
+  DevBuf<uint16_t> dio; DevBuf<uint8_t> dbins; DevBuf<unsigned long long> dbits;
   uint16_t io[2] = { *s0, *s1 };
-  HIPCHK(dio.alloc(4)); HIPCHK(dbins.alloc((size_t) nbins)); HIPCHK(dbits.alloc(8));
+  HIPCHK(dio.alloc(2)); HIPCHK(dbins.alloc((size_t) nbins)); HIPCHK(dbits.alloc(1));
   HIPCHK(hipMemcpy(dio.p, io, 4, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dbins.p, bins, (size_t) nbins, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(vvcx_leaf_cabac_kernel, dim3(1), dim3(VXD_NT), 0, 0, dio.as<uint16_t>(), (int) VX_CTX_RATE_REF[ctx], dbins.as<uint8_t>(), nbins, dbits.as<unsigned long long>());
+  hipLaunchKernelGGL(vvcx_leaf_cabac_kernel, dim3(1), dim3(VXD_NT), 0, 0, dio.p, (int) VX_CTX_RATE_REF[ctx], dbins.p, nbins, dbits.p);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpy(io, dio.p, 4, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(frac_bits, dbits.p, 8, hipMemcpyDeviceToHost));
   *s0 = io[0]; *s1 = io[1];
@@ -1578,13 +1524,13 @@ extern "C" int vvcx_rd_cost_batch(double lambda, const uint64_t *frac_bits, cons
 {
   if (!(lambda > 0.0) || !frac_bits || !dist || !cost || n < 0) return fail(VVCX_ERR_ARG, "bad argument");
   if (n == 0) return VVCX_OK;
-  HIPCHK(hipSetDevice(device));
-  DevBuf db, dd, dc;
-  HIPCHK(db.alloc((size_t) n * 8)); HIPCHK(dd.alloc((size_t) n * 8)); HIPCHK(dc.alloc((size_t) n * 8));
+  ON_DEVICE(device);
+  DevBuf<unsigned long long> db, dd; DevBuf<double> dc;
+  HIPCHK(db.alloc((size_t) n)); HIPCHK(dd.alloc((size_t) n)); HIPCHK(dc.alloc((size_t) n));
   HIPCHK(hipMemcpy(db.p, frac_bits, (size_t) n * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dd.p, dist, (size_t) n * 8, hipMemcpyHostToDevice));
   VxParams p; memset(&p, 0, sizeof p);
   p.lambda = lambda; p.dist_scale = (double) (1 << 15) / lambda;
-  hipLaunchKernelGGL(vvcx_leaf_rdcost_kernel, dim3((unsigned) ((n + VXD_NT - 1) / VXD_NT)), dim3(VXD_NT), 0, 0, p, db.as<unsigned long long>(), dd.as<unsigned long long>(), n, dc.as<double>());
+  hipLaunchKernelGGL(vvcx_leaf_rdcost_kernel, dim3((unsigned) ((n + VXD_NT - 1) / VXD_NT)), dim3(VXD_NT), 0, 0, p, db.p, dd.p, n, dc.p);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpy(cost, dc.p, (size_t) n * 8, hipMemcpyDeviceToHost));
   return VVCX_OK;
@@ -1593,10 +1539,10 @@ extern "C" int vvcx_rd_cost_batch(double lambda, const uint64_t *frac_bits, cons
 extern "C" int vvcx_scan_order(int w, int h, uint16_t *idx, int device)
 {
   if (!idx || !pow2_block(w, h)) return fail(VVCX_ERR_ARG, "bad argument");
-  HIPCHK(hipSetDevice(device));
+  ON_DEVICE(device);
   const int n = (w < 32 ? w : 32) * (h < 32 ? h : 32);
-  DevBuf d; HIPCHK(d.alloc((size_t) n * 2));
-  hipLaunchKernelGGL(vvcx_leaf_scan_kernel, dim3(1), dim3(VXD_NT), 0, 0, w, h, d.as<uint16_t>());
+  DevBuf<uint16_t> d; HIPCHK(d.alloc((size_t) n));
+  hipLaunchKernelGGL(vvcx_leaf_scan_kernel, dim3(1), dim3(VXD_NT), 0, 0, w, h, d.p);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpy(idx, d.p, (size_t) n * 2, hipMemcpyDeviceToHost));
   return VVCX_OK;
@@ -1619,11 +1565,11 @@ extern "C" int vvcx_mip_pred_batch(const int32_t *cases, int n, const int16_t *r
   }
   if (ro > n_refs || po > n_pred) return fail(VVCX_ERR_ARG, "reference / prediction buffers too small");
   if (n == 0) return VVCX_OK;
-  HIPCHK(hipSetDevice(device));
-  DevBuf dc, dr, dp; HIPCHK(dc.alloc(sizeof(VxMipCase) * (size_t) n)); HIPCHK(dr.alloc((size_t) ro * 2)); HIPCHK(dp.alloc((size_t) po * 2));
+  ON_DEVICE(device);
+  DevBuf<VxMipCase> dc; DevBuf<int16_t> dr, dp; HIPCHK(dc.alloc((size_t) n)); HIPCHK(dr.alloc((size_t) ro)); HIPCHK(dp.alloc((size_t) po));
   HIPCHK(hipMemcpy(dc.p, cs.data(), sizeof(VxMipCase) * (size_t) n, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(dr.p, refs, (size_t) ro * 2, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(vvcx_leaf_mip_kernel, dim3((unsigned) n), dim3(64), 0, 0, dc.as<VxMipCase>(), dr.as<int16_t>(), dp.as<int16_t>());
+  hipLaunchKernelGGL(vvcx_leaf_mip_kernel, dim3((unsigned) n), dim3(64), 0, 0, dc.p, dr.p, dp.p);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpy(pred, dp.p, (size_t) po * 2, hipMemcpyDeviceToHost));
   return VVCX_OK;
@@ -1636,13 +1582,13 @@ extern "C" int vvcx_forest_predict_batch(vvcx_handle *h, const int32_t *rows, in
   if (!h || !rows || !out || n < 0) return fail(VVCX_ERR_ARG, "bad argument");
   if (!h->f_ntrees) return fail(VVCX_ERR_STATE, "vvcx_set_forest first");
   if (n == 0) return VVCX_OK;
-  HIPCHK(hipSetDevice(h->cfg.device));
-  DevBuf dr, dout; HIPCHK(dr.alloc((size_t) n * 26 * 4)); HIPCHK(dout.alloc((size_t) n * 4));
+  ON_DEVICE(h->cfg.device);
+  DevBuf<int32_t> dr, dout; HIPCHK(dr.alloc((size_t) n * 26)); HIPCHK(dout.alloc((size_t) n));
   HIPCHK(hipMemcpy(dr.p, rows, (size_t) n * 26 * 4, hipMemcpyHostToDevice));
   VxParams p; memset(&p, 0, sizeof p);
-  p.f_node = h->f_node_d; p.f_value = h->f_value_d; p.f_root = h->f_root_d; p.f_ntrees = h->f_ntrees; p.f_nclasses = h->f_nclasses;
+  p.f_node = h->f_node_d.p; p.f_value = h->f_value_d.p; p.f_root = h->f_root_d.p; p.f_ntrees = h->f_ntrees; p.f_nclasses = h->f_nclasses;
   for (int c = 0; c < 8; c++) p.f_classes[c] = h->f_classes[c];
-  hipLaunchKernelGGL(vvcx_leaf_forest_kernel, dim3((unsigned) ((n + VXD_NT - 1) / VXD_NT)), dim3(VXD_NT), 0, 0, p, dr.as<int32_t>(), n, dout.as<int32_t>());
+  hipLaunchKernelGGL(vvcx_leaf_forest_kernel, dim3((unsigned) ((n + VXD_NT - 1) / VXD_NT)), dim3(VXD_NT), 0, 0, p, dr.p, n, dout.p);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpy(out, dout.p, (size_t) n * 4, hipMemcpyDeviceToHost));
   return VVCX_OK;
@@ -1653,13 +1599,13 @@ extern "C" int vvcx_transform_quant_batch(const int16_t *org, const int16_t *pre
 {
   if (!org || !pred || !lev || !rec || !sse || !cbf || n < 0 || !pow2_block(w, h) || (bit_depth != 8 && bit_depth != 10) || qp < 0 || qp > 75) return fail(VVCX_ERR_ARG, "bad argument");
   if (n == 0) return VVCX_OK;
-  HIPCHK(hipSetDevice(device));
+  ON_DEVICE(device);
   const size_t bytes = (size_t) n * w * h * 2;
-  DevBuf dorg, drec, dlev, dtmp, dout;
-  HIPCHK(dorg.alloc(bytes)); HIPCHK(drec.alloc(bytes)); HIPCHK(dlev.alloc(bytes)); HIPCHK(dtmp.alloc((size_t) n * 2048 * 4)); HIPCHK(dout.alloc((size_t) n * 16));
+  DevBuf<int16_t> dorg, drec, dlev; DevBuf<int32_t> dtmp; DevBuf<unsigned long long> dout;
+  HIPCHK(dorg.alloc(bytes / 2)); HIPCHK(drec.alloc(bytes / 2)); HIPCHK(dlev.alloc(bytes / 2)); HIPCHK(dtmp.alloc((size_t) n * 2048)); HIPCHK(dout.alloc((size_t) n * 2));
   HIPCHK(hipMemcpy(dorg.p, org, bytes, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(drec.p, pred, bytes, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(vvcx_leaf_trq_kernel, dim3((unsigned) n), dim3(VXD_NT), 0, 0, dorg.as<int16_t>(), drec.as<int16_t>(), dlev.as<int16_t>(), dtmp.as<int32_t>(), w, h, bit_depth, qp,
-                     dout.as<unsigned long long>());
+  hipLaunchKernelGGL(vvcx_leaf_trq_kernel, dim3((unsigned) n), dim3(VXD_NT), 0, 0, dorg.p, drec.p, dlev.p, dtmp.p, w, h, bit_depth, qp,
+                     dout.p);
   HIPCHK(hipGetLastError());
   std::vector<unsigned long long> o((size_t) n * 2);
   HIPCHK(hipMemcpy(lev, dlev.p, bytes, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(rec, drec.p, bytes, hipMemcpyDeviceToHost));
@@ -1674,20 +1620,20 @@ static int depquant_batch_impl(const int16_t *org, const int16_t *pred, int w, i
   if (!org || !pred || !lev || !rec || !sse || !cbf || !s0 || !s1 || n < 0 || !pow2_block(w, h) || (bit_depth != 8 && bit_depth != 10) || qp < 0 || qp > 75 || comp < 0 || comp > 2 ||
       !(lambda > 0.0) || (mts_idx != 0 && (mts_idx < 2 || mts_idx > 5 || comp != 0 || w > 32 || h > 32 || w < 4 || h < 4))) return fail(VVCX_ERR_ARG, "bad argument");
   if (n == 0) return VVCX_OK;
-  HIPCHK(hipSetDevice(device));
+  ON_DEVICE(device);
   const size_t bytes = (size_t) n * w * h * 2;
-  DevBuf dorg, drec, dlev, dtmp, dout, dctx, dtab, dscr;
-  HIPCHK(dorg.alloc(bytes)); HIPCHK(drec.alloc(bytes)); HIPCHK(dlev.alloc(bytes)); HIPCHK(dtmp.alloc((size_t) n * 2048 * 4)); HIPCHK(dout.alloc((size_t) n * 16));
-  HIPCHK(dctx.alloc(2 * VXD_NUM_CTX * 2)); HIPCHK(dtab.alloc(48 * sizeof(VxDqConst))); HIPCHK(dscr.alloc((size_t) n * VXD_OFF_CACHE));
+  DevBuf<int16_t> dorg, drec, dlev; DevBuf<int32_t> dtmp; DevBuf<unsigned long long> dout; DevBuf<uint16_t> dctx; DevBuf<VxDqConst> dtab; DevBuf<uint8_t> dscr;
+  HIPCHK(dorg.alloc(bytes / 2)); HIPCHK(drec.alloc(bytes / 2)); HIPCHK(dlev.alloc(bytes / 2)); HIPCHK(dtmp.alloc((size_t) n * 2048)); HIPCHK(dout.alloc((size_t) n * 2));
+  HIPCHK(dctx.alloc(2 * VXD_NUM_CTX)); HIPCHK(dtab.alloc(48)); HIPCHK(dscr.alloc((size_t) n * VXD_OFF_CACHE));
   HIPCHK(hipMemcpy(dorg.p, org, bytes, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(drec.p, pred, bytes, hipMemcpyHostToDevice));
   { uint16_t kept[2 * VXD_NUM_CTX]; ctx_from_reference_order(s0, s1, kept); HIPCHK(hipMemcpy(dctx.p, kept, sizeof kept, hipMemcpyHostToDevice)); }
   VxDqConst tab[48]; memset(tab, 0, sizeof tab);
   for (int lsum = 2; lsum <= 12; lsum++) tab[comp * 16 + lsum] = dq_consts_of(lsum, bit_depth, qp, lambda);
   HIPCHK(hipMemcpy(dtab.p, tab, sizeof tab, hipMemcpyHostToDevice));
   VxParams p; memset(&p, 0, sizeof p);
-  p.bit_depth = bit_depth; p.tools = VVCX_TOOL_DEPQUANT | VVCX_TOOL_MTS | (lfnst_idx ? VVCX_TOOL_LFNST : 0); p.dq_consts = dtab.as<VxDqConst>(); p.scratch = dscr.as<uint8_t>(); p.scratch_per_stream = VXD_OFF_CACHE;
-  hipLaunchKernelGGL(vvcx_leaf_dq_kernel, dim3((unsigned) n), dim3(VXD_NT), 0, 0, p, dctx.as<uint16_t>(), dorg.as<int16_t>(), drec.as<int16_t>(), dlev.as<int16_t>(), dtmp.as<int32_t>(),
-                     w, h, qp, comp, mts_idx, cbf_cb, dout.as<unsigned long long>(), (w >= 4 && h >= 4) ? lfnst_idx : 0, intra_dir);
+  p.bit_depth = bit_depth; p.tools = VVCX_TOOL_DEPQUANT | VVCX_TOOL_MTS | (lfnst_idx ? VVCX_TOOL_LFNST : 0); p.dq_consts = dtab.p; p.scratch = dscr.p; p.scratch_per_stream = VXD_OFF_CACHE;
+  hipLaunchKernelGGL(vvcx_leaf_dq_kernel, dim3((unsigned) n), dim3(VXD_NT), 0, 0, p, dctx.p, dorg.p, drec.p, dlev.p, dtmp.p,
+                     w, h, qp, comp, mts_idx, cbf_cb, dout.p, (w >= 4 && h >= 4) ? lfnst_idx : 0, intra_dir);
   HIPCHK(hipGetLastError());
   std::vector<unsigned long long> o((size_t) n * 2);
   HIPCHK(hipMemcpy(lev, dlev.p, bytes, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(rec, drec.p, bytes, hipMemcpyDeviceToHost));
@@ -1716,21 +1662,21 @@ extern "C" int vvcx_isp_tu_batch(const int16_t *org, const int16_t *pred, int tw
   const bool shape = tw >= 1 && th >= 1 && tw <= 64 && th <= 64 && !(tw & (tw - 1)) && !(th & (th - 1)) && tw * th >= 16;
   if (!org || !pred || !lev || !rec || !sse || !cbf || !s0 || !s1 || n < 0 || !shape || (bit_depth != 8 && bit_depth != 10) || qp < 0 || qp > 75 || !(lambda > 0.0)) return fail(VVCX_ERR_ARG, "bad argument");
   if (n == 0) return VVCX_OK;
-  HIPCHK(hipSetDevice(device));
+  ON_DEVICE(device);
   const size_t bytes = (size_t) n * tw * th * 2;
-  DevBuf dorg, drec, dlev, dtmp, dout, dctx, dtab, dscr;
-  HIPCHK(dorg.alloc(bytes)); HIPCHK(drec.alloc(bytes)); HIPCHK(dlev.alloc(bytes)); HIPCHK(dtmp.alloc((size_t) n * 2048 * 4)); HIPCHK(dout.alloc((size_t) n * 16));
-  HIPCHK(dctx.alloc(2 * VXD_NUM_CTX * 2)); HIPCHK(dtab.alloc(96 * sizeof(VxDqConst))); HIPCHK(dscr.alloc((size_t) n * VXD_OFF_CACHE));
+  DevBuf<int16_t> dorg, drec, dlev; DevBuf<int32_t> dtmp; DevBuf<unsigned long long> dout; DevBuf<uint16_t> dctx; DevBuf<VxDqConst> dtab; DevBuf<uint8_t> dscr;
+  HIPCHK(dorg.alloc(bytes / 2)); HIPCHK(drec.alloc(bytes / 2)); HIPCHK(dlev.alloc(bytes / 2)); HIPCHK(dtmp.alloc((size_t) n * 2048)); HIPCHK(dout.alloc((size_t) n * 2));
+  HIPCHK(dctx.alloc(2 * VXD_NUM_CTX)); HIPCHK(dtab.alloc(96)); HIPCHK(dscr.alloc((size_t) n * VXD_OFF_CACHE));
   HIPCHK(hipMemcpy(dorg.p, org, bytes, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(drec.p, pred, bytes, hipMemcpyHostToDevice));
   { uint16_t kept[2 * VXD_NUM_CTX]; ctx_from_reference_order(s0, s1, kept); HIPCHK(hipMemcpy(dctx.p, kept, sizeof kept, hipMemcpyHostToDevice)); }
   VxDqConst tab[96]; memset(tab, 0, sizeof tab);
   for (int lsum = 2; lsum <= 12; lsum++) tab[lsum] = dq_consts_of(lsum, bit_depth, qp, lambda);
   HIPCHK(hipMemcpy(dtab.p, tab, sizeof tab, hipMemcpyHostToDevice));
   VxParams p; memset(&p, 0, sizeof p);
-  p.bit_depth = bit_depth; p.tools = VVCX_TOOL_DEPQUANT | VVCX_TOOL_MTS | VVCX_TOOL_LFNST | VVCX_TOOL_ISP; p.dq_consts = dtab.as<VxDqConst>(); p.scratch = dscr.as<uint8_t>(); p.scratch_per_stream = VXD_OFF_CACHE;
+  p.bit_depth = bit_depth; p.tools = VVCX_TOOL_DEPQUANT | VVCX_TOOL_MTS | VVCX_TOOL_LFNST | VVCX_TOOL_ISP; p.dq_consts = dtab.p; p.scratch = dscr.p; p.scratch_per_stream = VXD_OFF_CACHE;
   p.lambda = lambda;
-  hipLaunchKernelGGL(vvcx_leaf_isp_kernel, dim3((unsigned) n), dim3(VXD_NT), 0, 0, p, dctx.as<uint16_t>(), dorg.as<int16_t>(), drec.as<int16_t>(), dlev.as<int16_t>(), dtmp.as<int32_t>(),
-                     tw, th, qp, cbf_inferred ? -1 : (int) VX_CTX_QtCbf[0] + 2 + (prev_cbf ? 1 : 0), dout.as<unsigned long long>());
+  hipLaunchKernelGGL(vvcx_leaf_isp_kernel, dim3((unsigned) n), dim3(VXD_NT), 0, 0, p, dctx.p, dorg.p, drec.p, dlev.p, dtmp.p,
+                     tw, th, qp, cbf_inferred ? -1 : (int) VX_CTX_QtCbf[0] + 2 + (prev_cbf ? 1 : 0), dout.p);
   HIPCHK(hipGetLastError());
   std::vector<unsigned long long> o((size_t) n * 2);
   HIPCHK(hipMemcpy(lev, dlev.p, bytes, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(rec, drec.p, bytes, hipMemcpyDeviceToHost));
@@ -1748,17 +1694,17 @@ extern "C" int vvcx_transform_skip_batch(const int16_t *resi, int w, int h, int 
   if (!resi || !lev || !resi_out || !abs_sum || !keep || !frac_bits || !s0 || !s1 || n < 0 || !pow2_block(w, h) || w < 4 || h < 4 || w > 32 || h > 32 || (bit_depth != 8 && bit_depth != 10) ||
       qp < 0 || qp > 75 || !(lambda > 0.0)) return fail(VVCX_ERR_ARG, "bad argument");
   if (n == 0) return VVCX_OK;
-  HIPCHK(hipSetDevice(device));
+  ON_DEVICE(device);
   const size_t bytes = (size_t) n * w * h * 2;
-  DevBuf dres, dout, dlev, dtmp, do2, dbits, dctx;
-  HIPCHK(dres.alloc(bytes)); HIPCHK(dout.alloc(bytes)); HIPCHK(dlev.alloc(bytes)); HIPCHK(dtmp.alloc((size_t) n * 2048 * 4)); HIPCHK(do2.alloc((size_t) n * 8)); HIPCHK(dbits.alloc((size_t) n * 8));
-  HIPCHK(dctx.alloc(2 * VXD_NUM_CTX * 2));
+  DevBuf<int16_t> dres, dout, dlev; DevBuf<int32_t> dtmp; DevBuf<int> do2; DevBuf<unsigned long long> dbits; DevBuf<uint16_t> dctx;
+  HIPCHK(dres.alloc(bytes / 2)); HIPCHK(dout.alloc(bytes / 2)); HIPCHK(dlev.alloc(bytes / 2)); HIPCHK(dtmp.alloc((size_t) n * 2048)); HIPCHK(do2.alloc((size_t) n * 2)); HIPCHK(dbits.alloc((size_t) n));
+  HIPCHK(dctx.alloc(2 * VXD_NUM_CTX));
   HIPCHK(hipMemcpy(dres.p, resi, bytes, hipMemcpyHostToDevice)); HIPCHK(hipMemset(dout.p, 0, bytes));
   { uint16_t kept[2 * VXD_NUM_CTX]; ctx_from_reference_order(s0, s1, kept); HIPCHK(hipMemcpy(dctx.p, kept, sizeof kept, hipMemcpyHostToDevice)); }
   VxParams p; memset(&p, 0, sizeof p);
   p.bit_depth = bit_depth; p.tools = VVCX_TOOL_DEPQUANT | VVCX_TOOL_LFNST | VVCX_TOOL_TS; p.lambda = lambda;
-  hipLaunchKernelGGL(vvcx_leaf_ts_kernel, dim3((unsigned) n), dim3(VXD_NT), 0, 0, p, dctx.as<uint16_t>(), dres.as<int16_t>(), dlev.as<int16_t>(), dout.as<int16_t>(), dtmp.as<int32_t>(), w, h, qp,
-                     do2.as<int>(), dbits.as<unsigned long long>());
+  hipLaunchKernelGGL(vvcx_leaf_ts_kernel, dim3((unsigned) n), dim3(VXD_NT), 0, 0, p, dctx.p, dres.p, dlev.p, dout.p, dtmp.p, w, h, qp,
+                     do2.p, dbits.p);
   HIPCHK(hipGetLastError());
   std::vector<int> o((size_t) n * 2);
   HIPCHK(hipMemcpy(lev, dlev.p, bytes, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(resi_out, dout.p, bytes, hipMemcpyDeviceToHost));
@@ -1772,8 +1718,8 @@ extern "C" int vvcx_transform_skip_batch(const int16_t *resi, int w, int h, int 
 static int payload_of_tile(vvcx_handle *h, int frame, int tile, uint8_t *buf, int cap, int *nbytes, int *sizes, int max_sizes, int *n_sizes)
 {
   if (!h || frame < 0 || frame >= h->n_frames || tile < 0 || tile >= h->ntiles) return fail(VVCX_ERR_ARG, "bad argument");
-  if (!h->payload_d) return fail(VVCX_ERR_STATE, "handle was created without emit_payload");
-  DevGuard guard(h->cfg.device);
+  if (!h->payload_d.p) return fail(VVCX_ERR_STATE, "handle was created without emit_payload");
+  ON_DEVICE(h->cfg.device);
   const int sub0 = h->tile_sub0[(size_t) tile], ns = h->tile_nsub[(size_t) tile];
   if (n_sizes) *n_sizes = ns;
   if (sizes && max_sizes < ns) return fail(VVCX_ERR_ARG, "room for %d sub-stream sizes, the tile has %d", max_sizes, ns);
@@ -1782,11 +1728,11 @@ static int payload_of_tile(vvcx_handle *h, int frame, int tile, uint8_t *buf, in
     const size_t s = (size_t) frame * h->nsub + (size_t) (sub0 + k);
     if (h->next_idx[s] != (int) h->sub_ctus[(size_t) (sub0 + k)].size()) return fail(VVCX_ERR_STATE, "tile %d of frame %d is not completely coded yet", tile, frame);
     uint32_t st[8];
-    HIPCHK(hipMemcpy(st, (const uint8_t *) h->arith_d + s * 32, 32, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(st, (const uint8_t *) h->arith_d.p + s * 32, 32, hipMemcpyDeviceToHost));
     const uint32_t n = st[7];                        // Arith::n
     if (n > h->payload_cap[s]) return fail(VVCX_ERR_STATE, "payload of tile %d exceeds the %u bytes reserved", tile, h->payload_cap[s]);
     if (sizes) sizes[k] = (int) n;
-    if (buf && total + n <= (size_t) cap) HIPCHK(hipMemcpy(buf + total, h->payload_d + h->payload_off[s], n, hipMemcpyDeviceToHost));
+    if (buf && total + n <= (size_t) cap) HIPCHK(hipMemcpy(buf + total, h->payload_d.p + h->payload_off[s], n, hipMemcpyDeviceToHost));
     total += n;
   }
   if (nbytes) *nbytes = (int) total;
@@ -1801,14 +1747,14 @@ extern "C" int vvcx_enable_training_dump(vvcx_handle *h, int cap_rows)
   // the features look at the CUs above-right and below-left of a node through the unrestricted neighbour lookup; under WPP those belong to rows that run at their own
   // pace, so the rows would depend on timing (the same reason VVCX_TOOL_FAST is refused together with WPP)
   if (cap_rows > 0 && (h->cfg.tools & VVCX_TOOL_WPP)) return fail(VVCX_ERR_UNSUPPORTED, "the training dump is not available on a WPP handle");
-  DevGuard guard(h->cfg.device);
-  (void) hipFree(h->train_rows_d); (void) hipFree(h->train_n_d); h->train_rows_d = nullptr; h->train_n_d = nullptr; h->train_cap = 0;
+  ON_DEVICE(h->cfg.device);
+  h->train_cap = 0; h->train_rows_d.release(); h->train_n_d.release();
   if (cap_rows == 0) return VVCX_OK;
-  if (hipMalloc((void **) &h->train_rows_d, (size_t) cap_rows * 28 * 4) != hipSuccess || hipMalloc((void **) &h->train_n_d, 4) != hipSuccess) {
-    (void) hipFree(h->train_rows_d); h->train_rows_d = nullptr;
+  if (h->train_rows_d.alloc((size_t) cap_rows * 28) != hipSuccess || h->train_n_d.alloc(1) != hipSuccess) {
+    h->train_rows_d.release();                        // (a dump is on while the rows exist)
     return fail(VVCX_ERR_DEVICE, "device allocation of %d training rows failed", cap_rows);
   }
-  HIPCHK(hipMemset(h->train_n_d, 0, 4));
+  HIPCHK(hipMemset(h->train_n_d.p, 0, 4));
   h->train_cap = cap_rows;
   return VVCX_OK;
 }
@@ -1816,13 +1762,13 @@ extern "C" int vvcx_get_training_rows(vvcx_handle *h, int32_t *rows, int max_row
 {
   NOT_PENDING(h);
   if (!h || !n_rows || max_rows < 0 || (!rows && max_rows)) return fail(VVCX_ERR_ARG, "bad argument");
-  if (!h->train_rows_d) return fail(VVCX_ERR_STATE, "vvcx_enable_training_dump first");
-  DevGuard guard(h->cfg.device);
+  if (!h->train_rows_d.p) return fail(VVCX_ERR_STATE, "vvcx_enable_training_dump first");
+  ON_DEVICE(h->cfg.device);
   uint32_t n = 0;
-  HIPCHK(hipMemcpy(&n, h->train_n_d, 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&n, h->train_n_d.p, 4, hipMemcpyDeviceToHost));
   *n_rows = (int) n;                                  // rows asked for; more than the capacity means the tail was dropped
   const int have = (int) (n < (uint32_t) h->train_cap ? n : (uint32_t) h->train_cap), take = have < max_rows ? have : max_rows;
-  if (take) HIPCHK(hipMemcpy(rows, h->train_rows_d, (size_t) take * 28 * 4, hipMemcpyDeviceToHost));
+  if (take) HIPCHK(hipMemcpy(rows, h->train_rows_d.p, (size_t) take * 28 * 4, hipMemcpyDeviceToHost));
   return VVCX_OK;
 }
 extern "C" int vvcx_get_payload(vvcx_handle *h, int frame, int tile, uint8_t *buf, int cap, int *nbytes)

@@ -16,12 +16,11 @@
 // Pinned by tests/golden/lmcs_analysis.npz: the models the reference's own EncReshape (compiled in place, oracle/_ref) chose for 29 pictures.
 #include <hip/hip_runtime.h>
 #include "vvcx.h"
+#include "vvcx_host.h"        // DevBuf; errors go through vvcx_fail_msg_ (vvcx_api.hip: sets what vvcx_last_error returns)
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <vector>
-
-extern "C" int vvcx_fail_msg_(int code, const char *msg);      // vvcx_api.hip: sets what vvcx_last_error returns
 
 namespace {
 constexpr int kBins = 16;            // luma bins of the analysis and of the model (PIC_CODE_CW_BINS)
@@ -113,29 +112,23 @@ __global__ void lmcs_chroma_moments(const T *cb, const T *cr, int stride_b, int 
   }
 }
 
-struct DevMem {                      // frees what it allocated
-  void *p = nullptr;
-  ~DevMem() { if (p) (void) hipFree(p); }
-  hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
-};
-
 // the statistics of one picture whose planes are in device memory
 template <typename T>
 int picture_stats(const void *const org[3], const int stride[3], int w, int h, int bd, StatOut &st)
 {
   const int win = (w < h ? w : h) / 240 > 0 ? (w < h ? w : h) / 240 : 1;
   const size_t np = (size_t) w * h, runs = (size_t) ((w + kRun - 1) / kRun) * h;
-  DevMem rs, rq, part, pcnt, out;
-  if (rs.alloc(np * 4) != hipSuccess || rq.alloc(np * 4) != hipSuccess || part.alloc(runs * kBins * 8) != hipSuccess || pcnt.alloc(runs * kBins * 4) != hipSuccess ||
-      out.alloc(sizeof(StatOut)) != hipSuccess) return vvcx_fail_msg_(VVCX_ERR_DEVICE, "vvcx_lmcs_analyze: device allocation failed");
+  DevBuf<uint32_t> rs, rq, pcnt; DevBuf<double> part; DevBuf<StatOut> out;
+  if (rs.alloc(np) != hipSuccess || rq.alloc(np) != hipSuccess || part.alloc(runs * kBins) != hipSuccess || pcnt.alloc(runs * kBins) != hipSuccess ||
+      out.alloc(1) != hipSuccess) return vvcx_fail_msg_(VVCX_ERR_DEVICE, "vvcx_lmcs_analyze: device allocation failed");
   if (hipMemset(out.p, 0, sizeof(StatOut)) != hipSuccess) return vvcx_fail_msg_(VVCX_ERR_DEVICE, "vvcx_lmcs_analyze: hipMemset failed");
   const unsigned T256 = 256;
-  hipLaunchKernelGGL(lmcs_row_sums<T>, dim3((unsigned) ((np + T256 - 1) / T256)), dim3(T256), 0, 0, (const T *) org[0], stride[0], w, h, win, (uint32_t *) rs.p, (uint32_t *) rq.p);
-  hipLaunchKernelGGL(lmcs_bin_terms<T>, dim3((unsigned) ((runs + T256 - 1) / T256)), dim3(T256), 0, 0, (const T *) org[0], stride[0], w, h, win, bd, (const uint32_t *) rs.p,
-                     (const uint32_t *) rq.p, (double *) part.p, (uint32_t *) pcnt.p, (StatOut *) out.p);
-  hipLaunchKernelGGL(lmcs_fold, dim3(1), dim3(kSlices * kBins), 0, 0, (const double *) part.p, (const uint32_t *) pcnt.p, runs, (StatOut *) out.p);
+  hipLaunchKernelGGL(lmcs_row_sums<T>, dim3((unsigned) ((np + T256 - 1) / T256)), dim3(T256), 0, 0, (const T *) org[0], stride[0], w, h, win, rs.p, rq.p);
+  hipLaunchKernelGGL(lmcs_bin_terms<T>, dim3((unsigned) ((runs + T256 - 1) / T256)), dim3(T256), 0, 0, (const T *) org[0], stride[0], w, h, win, bd, rs.p,
+                     rq.p, part.p, pcnt.p, out.p);
+  hipLaunchKernelGGL(lmcs_fold, dim3(1), dim3(kSlices * kBins), 0, 0, part.p, pcnt.p, runs, out.p);
   hipLaunchKernelGGL(lmcs_chroma_moments<T>, dim3((unsigned) ((h / 2 + T256 - 1) / T256)), dim3(T256), 0, 0, (const T *) org[1], (const T *) org[2], stride[1], stride[2], w / 2, h / 2,
-                     (StatOut *) out.p);
+                     out.p);
   if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return vvcx_fail_msg_(VVCX_ERR_DEVICE, "vvcx_lmcs_analyze: statistics kernels failed");
   if (hipMemcpy(&st, out.p, sizeof st, hipMemcpyDeviceToHost) != hipSuccess) return vvcx_fail_msg_(VVCX_ERR_DEVICE, "vvcx_lmcs_analyze: copy back failed");
   return VVCX_OK;
@@ -434,7 +427,7 @@ extern "C" int vvcx_lmcs_analyze(const void *const org[3], const int stride[3], 
   if (rc != VVCX_OK) return rc;
   no_model(slice);
   if (bit_depth < 10) return VVCX_OK;
-  DevMem d[3]; const void *dev[3];
+  DevBuf<uint8_t> d[3]; const void *dev[3];
   for (int c = 0; c < 3; c++) {
     const size_t bytes = (size_t) stride[c] * (c ? pic_h / 2 : pic_h) * 2;
     if (d[c].alloc(bytes) != hipSuccess || hipMemcpy(d[c].p, org[c], bytes, hipMemcpyHostToDevice) != hipSuccess) return vvcx_fail_msg_(VVCX_ERR_DEVICE, "vvcx_lmcs_analyze: upload of the picture failed");

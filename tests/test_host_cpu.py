@@ -488,6 +488,47 @@ def test_deblocking_kernel_on_cpu_emulator_matches_oracle(emu_so, case):
     enc.close()
 
 
+def test_loop_filters_recover_from_a_failed_device_allocation(emu_so):
+    """A device allocation that fails inside a loop-filter entry point is a VVCX_ERR_DEVICE return that leaves the handle usable: the next call allocates again and gives
+    the planes / statistics of a handle that never saw a failure.  (A capacity recorded in front of the allocation made the next call skip it and launch the kernels
+    on a null pointer.)  The failure comes from the emulator's hipMalloc (hipemu_fail_allocs); the product library has no such switch."""
+    w, h, qp = 64, 48, 32
+    planes = pkg.synth_frame(w, h, 0, 8, 7, chroma_texture=0.5)
+    sp = pkg.slice_params(qp)
+    sao_prm, alf_prm = O.sao_params(5, w, h, 1, 1), O.alf_params(6, w, h)
+
+    def coded():
+        enc = pkg.VvcxEncoder(w, h, 8, tools=pkg.TOOLS_DEFAULT, lib_path=emu_so)
+        enc.set_slice(sp["qp"], sp["qp_c"], sp["lam"], sp["dist_weight"])
+        org = [np.ascontiguousarray(p) for p in planes]; rec = [np.zeros_like(p) for p in planes]
+        enc.bind_frames([([p.ctypes.data for p in org], [p.ctypes.data for p in rec], [p.shape[1] for p in org])])
+        enc.compress_bound_frames()
+        return enc, org, rec
+
+    stages = [("deblock", lambda e: e.deblock_bound_frames()), ("sao statistics", lambda e: e.sao_statistics_bound_frames(1)[0]),
+              ("sao", lambda e: e.sao_bound_frames(sao_prm)), ("alf", lambda e: e.alf_bound_frames([alf_prm]))]
+    enc, org, rec = coded()
+    ref, rorg, rrec = coded()
+    assert all(np.array_equal(a, b) for a, b in zip(rec, rrec))
+    arm = enc.L.hipemu_fail_allocs; arm.argtypes = [C.c_int]; arm.restype = None
+    try:
+        for name, call in stages:
+            before = [r.copy() for r in rec]
+            arm(1)
+            with pytest.raises(pkg.VvcxError, match="vvcx error -3"):      # VVCX_ERR_DEVICE
+                call(enc)
+            assert all(np.array_equal(a, b) for a, b in zip(rec, before)), name      # nothing ran
+            got, want = call(enc), call(ref)
+            assert all(np.array_equal(a, b) for a, b in zip(rec, rrec)), name
+            if name == "sao statistics":
+                assert np.array_equal(got, want) and got[..., 0, :].sum() > 0
+            else:
+                assert any((a != b).any() for a, b in zip(rec, before)), name      # the filter did move samples
+    finally:
+        arm(0)
+    enc.close(); ref.close()
+
+
 def test_training_set_dump_on_cpu_emulator_matches_oracle(emu_so):
     """vvcx_enable_training_dump / vvcx_get_training_rows (the fork's GET_TRAINING_SET): every qualifying luma node of the plain full search leaves its 26 features, its
     complexity class and the partition the search chose; the rows equal the oracle's dump (orc_set_training_dump) - all six labels occur - and the search itself is unchanged."""

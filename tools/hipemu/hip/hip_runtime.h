@@ -135,7 +135,9 @@ inline hipError_t hipOccupancyMaxActiveBlocksPerMultiprocessor(int *v, const voi
 #ifndef HIPEMU_REDZONE
 #define HIPEMU_REDZONE (4u << 20)
 #endif
+// hipemu_fail_allocs(n) (hipemu.cpp) makes the next n hipMalloc calls fail: how the tests reach the C-ABI layer's out-of-memory paths, which no GPU test may provoke.
 namespace hipemu {
+extern int g_fail_allocs;
 struct AllocHdr { size_t n; uint64_t magic; };
 inline void check_zone(const unsigned char *z, size_t n, const char *what, const void *user)
 {
@@ -144,6 +146,7 @@ inline void check_zone(const unsigned char *z, size_t n, const char *what, const
 }
 inline hipError_t hipMalloc(void **p, size_t n)
 {
+  if (hipemu::g_fail_allocs > 0) { hipemu::g_fail_allocs--; return 2; }
   if (!n) n = 1;
   unsigned char *raw = (unsigned char *) malloc(sizeof(hipemu::AllocHdr) + 2 * (size_t) HIPEMU_REDZONE + n);
   if (!raw) return 2;

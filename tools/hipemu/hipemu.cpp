@@ -26,6 +26,8 @@ hipemu_switch:
 )");
 namespace hipemu {
 Block *g_block; Fiber *g_cur; void *g_sched_sp; dim3 g_blockIdx, g_blockDim, g_gridDim;
+int g_fail_allocs = 0;
+extern "C" void hipemu_fail_allocs(int n) { g_fail_allocs = n; }
 static std::function<void()> *g_body;
 static void trampoline() { (*g_body)(); g_cur->done = true; for (;;) hipemu_switch(&g_cur->sp, g_sched_sp); }
 void launch(std::function<void()> body, dim3 grid, dim3 block)
