@@ -263,7 +263,8 @@ def gen_partition():
 
 def gen_trquant():
     """One luma transform block through the reference's TrQuant::transformNxN (xT + plain Quant::quant) and
-    invTransformNxN (dequant + xIT): residual in, levels and reconstructed residual out, for every block shape."""
+    invTransformNxN (dequant + xIT): residual in, levels and reconstructed residual out, for every block shape.  The residuals are smooth and small (Gaussian plus one slow
+    sinusoid, amplitude 2^bd / 4: |r| <= 56 at 8 bit, <= 214 at 10 bit); gen_trquant_range covers the full range +-(2^bd - 1)."""
     meta, resi_all, lev_all, out_all = [], [], [], []
     for bd, qp in ((8, 22), (8, 37), (10, 32)):
         env = R.ref_env_create(192, 192, bd)
@@ -286,7 +287,7 @@ def gen_trquant():
 def gen_trquant_mts():
     """Explicit MTS through the reference's TrQuant: (1) transformNxN / invTransformNxN with tu.mtsIdx 2..5 (DST-VII / DCT-VIII pairs,
     32-point zero-out) for every luma shape up to 32; (2) the candidate pruning overload (CL/TrQuant.cpp:1049-1124) on the list
-    {DCT2, 2, 3, 4, 5} with MTSIntraMaxCand 3."""
+    {DCT2, 2, 3, 4, 5} with MTSIntraMaxCand 3.  Smooth residuals of amplitude 2^bd / 4; the full range is gen_trquant_range's."""
     R.ref_env_tr_quant_mts.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 4
     R.ref_env_mts_prune.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 2
     g = np.random.default_rng(20260)
@@ -318,7 +319,7 @@ def gen_depquant():
     """Dependent quantisation through the reference: TrQuant::transformNxN with the slice's dep_quant flag on (DepQuant::quant →
     DQIntern::DepQuant::quant, CL/DepQuant.cpp:1592-1735) and invTransformNxN (Quantizer::dequantBlock 741-810), for luma blocks of every
     shape (DCT-II and explicit MTS pairs), Cb and Cr blocks (Cr with both values of tu.cbf[Cb]), sparse to dense residuals (the dense ones
-    exhaust the regular-bin budget), context models that have been adapted by random bins."""
+    exhaust the regular-bin budget), context models that have been adapted by random bins.  Residual amplitude 2^bd / 4; the full range is gen_trquant_range's."""
     R.ref_env_depquant.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_double, C.c_int] + [C.c_void_p] * 7
     R.ref_ctx_init.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 3
     g = np.random.default_rng(20262)
@@ -365,7 +366,8 @@ def gen_lfnst():
     """LFNST through the reference: TrQuant::transformNxN / invTransformNxN of blocks of a CU with lfnstIdx 1 / 2 (and 0 as the control) --
     the zero-out of the primary transform (xT 855-868), xFwdLfnst / xInvLfnst (CL/TrQuant.cpp:319-560) with the kernel set and transposition
     derived from the intra mode after the wide-angle mapping, followed by DepQuant (first tested position 7 / 15) or the plain quantiser (its
-    8 / 16 first buffer positions).  Luma blocks of every shape with every intra mode class, MIP CUs (planar set), Cb / Cr blocks."""
+    8 / 16 first buffer positions).  Luma blocks of every shape with every intra mode class, MIP CUs (planar set), Cb / Cr blocks.  Residual amplitude 2^bd / 4; the full
+    range is gen_trquant_range's."""
     R.ref_env_trquant_lfnst.argtypes = [C.c_void_p] + [C.c_int] * 10 + [C.c_double, C.c_int] + [C.c_void_p] * 7
     R.ref_ctx_init.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 3
     g = np.random.default_rng(20263)
@@ -699,7 +701,8 @@ def gen_bitstream_lfnst():
 def gen_ts():
     """Transform skip through the reference: the {DCT2, TS} pruning of TrQuant::transformNxN (CL/TrQuant.cpp:1049-1124), xTransformSkip, RDOQ-TS
     (QuantRDOQ::xRateDistOptQuantTS, reached through DepQuant::quant for MTS_SKIP luma blocks) with rates from adapted context models, Quant::dequant
-    and xITransformSkip, for every luma shape up to 32x32 (TransformSkipLog2MaxSize 5), sparse (screen-content like) to dense residuals, 8 / 10 bit."""
+    and xITransformSkip, for every luma shape up to 32x32 (TransformSkipLog2MaxSize 5), sparse (screen-content like) to dense residuals, 8 / 10 bit.  Residual amplitude
+    2^bd / 4; the full range is gen_trquant_range's."""
     R.ref_env_trquant_ts.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_double] + [C.c_void_p] * 8
     R.ref_ctx_init.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 3
     g = np.random.default_rng(20266)
@@ -746,7 +749,8 @@ def gen_ts():
 def gen_isp():
     """The transform path of ISP sub-partitions through the reference: TrQuant::transformNxN / invTransformNxN of a TU of a CU with cu.ispMode set -- implicit DST-VII for
     sides of 4..16 (getTrTypes), the 1-D transforms of Nx1 / 1xN blocks, DepQuant on 1xN / 2xN / Nx1 / Nx2 blocks with the ISP cbf contexts (previous sub-partition
-    coded or not, inferred last cbf) -- for every CU shape that can use ISP, both split directions, first / middle / last sub-partitions."""
+    coded or not, inferred last cbf) -- for every CU shape that can use ISP, both split directions, first / middle / last sub-partitions.  Residual amplitude 2^bd / 4; the
+    full range is gen_trquant_range's."""
     R.ref_env_trquant_isp.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_double, C.c_int, C.c_int] + [C.c_void_p] * 8
     R.ref_ctx_init.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 3
     g = np.random.default_rng(20267)
@@ -786,6 +790,169 @@ def gen_isp():
                         resi=np.concatenate(resi_all), lev=np.concatenate(lev_all), resi_out=np.concatenate(out_all))
     m = np.array(meta)
     print("isp cases", len(meta), "non-zero", int((m[:, 11] > 0).sum()), "TU shapes", sorted(set((int(r[7]), int(r[8])) for r in m)))
+
+
+RANGE_PATTERNS = ("dc+", "dc-", "checker", "vstripes", "hstripes", "hstep", "vstep", "impulses", "zeroout", "uniform", "twovalued")
+RANGE_QPS = (4, 27, 51)
+RANGE_RANDOM_QPS = {"a": (27,), "b": (27,), "c": (), "d": (27,), "e": (27,)}       # the two random patterns keep one QP (none under LFNST): their outputs do not compress, and the fixture stays below the size of the largest sibling
+RANGE_LFNST_DIRS = (0, 1, 34, 66)             # for the same reason one direction per (pattern, lfnst_idx, QP), rotating: every direction still meets every pattern and index
+RANGE_LUMA_SHAPES = ((32, 4), (32, 32), (64, 8), (32, 64), (64, 64),          # 32 / 64-point rows: the matrix-core forward stage of the device
+                     (4, 4), (16, 16), (4, 64), (8, 8), (16, 32))             # vector path; 16x32 is the smallest block above the device's 256-sample LDS buffers without 32-point rows
+
+
+def range_pattern(pat, w, h, bd):
+    """(org, pred), int16 [h, w] with values in [0, 2^bd - 1], of pattern family pat: org - pred spans +-(2^bd - 1)"""
+    mx = (1 << bd) - 1
+    yy, xx = np.mgrid[0:h, 0:w]
+    name = RANGE_PATTERNS[pat]
+    if name in ("uniform", "twovalued"):
+        g = np.random.default_rng([20269, w, h, bd, pat])
+        if name == "uniform":
+            org, pred = g.integers(0, mx + 1, (h, w)), g.integers(0, mx + 1, (h, w))
+        else:
+            org, pred = mx * g.integers(0, 2, (h, w)), mx * g.integers(0, 2, (h, w))
+    elif name == "impulses":                      # +max at (0, 0), -max at (w - 1, h - 1), a flat pair elsewhere
+        org = np.full((h, w), mx // 2); pred = org.copy()
+        org[0, 0], pred[0, 0] = mx, 0
+        org[h - 1, w - 1], pred[h - 1, w - 1] = 0, mx
+    else:
+        if name == "dc+": pos = np.ones((h, w), bool)
+        elif name == "dc-": pos = np.zeros((h, w), bool)
+        elif name == "checker": pos = ((xx + yy) & 1) == 0
+        elif name == "vstripes": pos = (xx & 1) == 0
+        elif name == "hstripes": pos = (yy & 1) == 0
+        elif name == "hstep": pos = xx < max(w // 2, 1)
+        elif name == "vstep": pos = yy < max(h // 2, 1)
+        else:                                     # the sign of the last DCT-II row the 64-point zero-out keeps, along both axes
+            kx, ky = min(w, 32) - 1, min(h, 32) - 1
+            pos = (np.cos((2 * xx + 1) * kx * np.pi / (2 * w)) * np.cos((2 * yy + 1) * ky * np.pi / (2 * h))) > 0
+        org = np.where(pos, mx, 0); pred = mx - org
+    return np.ascontiguousarray(org, np.int16), np.ascontiguousarray(pred, np.int16)
+
+
+def gen_trquant_range():
+    """The transform / quantiser leaves at the full legal range of org - pred, +-(2^bd - 1): eleven (org, pred) pattern families (flat, checkerboard, stripes, step edges,
+    impulses, the sign pattern of the last DCT-II row the zero-out keeps, uniform and two-valued noise) on the smallest shapes that reach every code path of the device,
+    slice QP 4 / 27 / 51, 8 and 10 bit, through the entry points gen_trquant / gen_depquant / gen_lfnst / gen_ts / gen_isp drive: (a) the plain quantiser, (b) DepQuant incl.
+    explicit MTS and Cb / Cr blocks, (c) LFNST over DepQuant, (d) transform skip with RDOQ-TS, (e) ISP sub-partition blocks.  org and pred are kept as two planes (a pool the
+    cases index: a pattern is the same for every QP and family); the references receive org - pred."""
+    R.ref_env_depquant.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_double, C.c_int] + [C.c_void_p] * 7
+    R.ref_env_trquant_lfnst.argtypes = [C.c_void_p] + [C.c_int] * 10 + [C.c_double, C.c_int] + [C.c_void_p] * 7
+    R.ref_env_trquant_ts.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_double] + [C.c_void_p] * 8
+    R.ref_env_trquant_isp.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_double, C.c_int, C.c_int] + [C.c_void_p] * 8
+    R.ref_ctx_init.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 3
+    g = np.random.default_rng(20268)
+    nctx = R.ref_ctx_count()
+    pool_org, pool_pred, pool_off, pool_len = [], [], {}, [0]
+
+    def inputs(pat, w, h, bd):
+        key = (pat, w, h, bd)
+        if key not in pool_off:
+            o, p = range_pattern(pat, w, h, bd)
+            pool_off[key] = pool_len[0]; pool_len[0] += w * h
+            pool_org.append(o.ravel()); pool_pred.append(p.ravel())
+        i = list(pool_off).index(key)
+        return pool_off[key], pool_org[i], pool_pred[i], np.ascontiguousarray(pool_org[i] - pool_pred[i])
+
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_lib as O
+    OL = O.lib()                                  # only for the report: the reference keeps its coefficients to itself, so the largest one is read from the oracle's forward transform
+
+    def coef_peak(resi, w, h, bd, mts):
+        coef = np.zeros(w * h, np.int32)
+        OL.orc_fwd_2d_mts(P(resi), w, w, h, bd, mts, P(coef))
+        return int(np.abs(coef).max())
+
+    fam = {f: dict(meta=[], lam=[], lev=[], out=[]) for f in "abcde"}
+    cpeak = {"a": 0, "b": 0}
+    ctx_all = []
+    peak = {f: [0, 0] for f in "abcde"}          # largest |level|, largest |reconstructed residual| per family
+
+    def keep(f, meta, lam, lev, ro):
+        assert np.abs(lev).max() < 32768
+        fam[f]["meta"].append(meta); fam[f]["lam"].append(lam); fam[f]["lev"].append(lev.astype(np.int16)); fam[f]["out"].append(ro)
+        peak[f][0] = max(peak[f][0], int(np.abs(lev).max())); peak[f][1] = max(peak[f][1], int(np.abs(ro.astype(np.int32)).max()))
+
+    def qps_of(f, pat):
+        return RANGE_RANDOM_QPS[f] if RANGE_PATTERNS[pat] in ("uniform", "twovalued") else RANGE_QPS
+
+    gi = 0
+    for bd in (8, 10):
+        env = R.ref_env_create(192, 192, bd)
+        for qp in RANGE_QPS:
+            s0 = np.zeros(nctx, np.uint16); s1 = np.zeros(nctx, np.uint16); rate = np.zeros(nctx, np.uint8)
+            R.ref_ctx_init(qp, 2, P(s0), P(s1), P(rate))
+            for i in range(nctx):                  # adapted context models, as gen_ts / gen_depquant take them
+                n = int(g.integers(0, 24)); bins = (g.random(n) < g.random()).astype(np.uint8)
+                a = s0[i:i + 1].copy(); b = s1[i:i + 1].copy()
+                if n: R.ref_ctx_code_bins(P(a), P(b), int(rate[i]), P(bins), n)
+                s0[i] = a[0]; s1[i] = b[0]
+            ctx_all.append(np.stack([s0, s1]))
+            lam0 = 0.57 * 2.0 ** ((qp + 6 * (bd - 8) - 12) / 3.0) * 2.0 ** (0.25 / 3.0)
+            for pat in range(len(RANGE_PATTERNS)):
+                # (a) plain quantiser, every luma shape
+                for (w, h) in RANGE_LUMA_SHAPES if qp in qps_of("a", pat) else ():
+                    off, _, _, resi = inputs(pat, w, h, bd)
+                    R.ref_env_reset(env)
+                    lev = np.zeros(w * h, np.int32); ro = np.zeros(w * h, np.int16); a = C.c_int()
+                    assert R.ref_env_tr_quant(env, 0, 0, w, h, qp, P(resi), P(lev), P(ro), C.byref(a)) == 0
+                    keep("a", (bd, qp, w, h, pat, off, a.value), lam0, lev, ro)
+                    cpeak["a"] = max(cpeak["a"], coef_peak(resi, w, h, bd, 0))
+                # (b) dependent quantiser: every luma shape, explicit MTS on 16x16 / 32x32, Cb 2x8 / 8x2, Cr 4x4 with both values of cbf_cb
+                cases = [(0, w, h, 0, 0) for (w, h) in RANGE_LUMA_SHAPES] + [(0, n, n, m, 0) for n in (16, 32) for m in (2, 3, 4, 5)]
+                cases += [(1, 2, 8, 0, 0), (1, 8, 2, 0, 0), (2, 4, 4, 0, 0), (2, 4, 4, 0, 1)]
+                for (comp, w, h, mts, cbf_cb) in cases if qp in qps_of("b", pat) else ():
+                    off, _, _, resi = inputs(pat, w, h, bd)
+                    R.ref_env_reset(env)
+                    lam = lam0 * (1.0, 0.8, 1.3)[comp]
+                    lev = np.zeros(w * h, np.int32); ro = np.zeros(w * h, np.int16); a = C.c_int(); qu = C.c_int()
+                    cw, chh = (w, h) if comp == 0 else (2 * w, 2 * h)
+                    assert R.ref_env_depquant(env, comp, 0, 0, cw, chh, qp, mts, lam, cbf_cb, P(s0), P(s1), P(resi), P(lev), P(ro), C.byref(a), C.byref(qu)) == 0
+                    keep("b", (bd, qp, comp, w, h, mts, cbf_cb, qu.value, a.value, gi, pat, off), lam, lev, ro)
+                    cpeak["b"] = max(cpeak["b"], coef_peak(resi, w, h, bd, mts))
+                # (c) LFNST over the trellis
+                for (w, h) in ((4, 4), (8, 8), (16, 16), (32, 32)) if qp in qps_of("c", pat) else ():
+                    for li in (1, 2):
+                        for d in (RANGE_LFNST_DIRS[(pat + li + RANGE_QPS.index(qp)) % 4],):
+                            off, _, _, resi = inputs(pat, w, h, bd)
+                            R.ref_env_reset(env)
+                            lev = np.zeros(w * h, np.int32); ro = np.zeros(w * h, np.int16); a = C.c_int(); qu = C.c_int()
+                            assert R.ref_env_trquant_lfnst(env, 0, 0, 0, w, h, qp, li, d, 0, 1, lam0, 0, P(s0), P(s1), P(resi), P(lev), P(ro), C.byref(a), C.byref(qu)) == 0
+                            keep("c", (bd, qp, 0, w, h, d, 0, li, 1, 0, a.value, gi, qu.value, pat, off), lam0, lev, ro)
+                # (d) transform skip with RDOQ-TS: the patterns as bare residuals
+                for (w, h) in ((4, 4), (8, 8), (32, 4), (32, 32)) if qp in qps_of("d", pat) else ():
+                    off, _, _, resi = inputs(pat, w, h, bd)
+                    R.ref_env_reset(env)
+                    lev = np.zeros(w * h, np.int32); ro = np.zeros(w * h, np.int16); a = C.c_int(); kp = C.c_int(); qu = C.c_int()
+                    assert R.ref_env_trquant_ts(env, 0, 0, w, h, qp, lam0, P(s0), P(s1), P(resi), P(lev), P(ro), C.byref(a), C.byref(kp), C.byref(qu)) == 0
+                    keep("d", (bd, qp, w, h, pat, kp.value, qu.value, a.value, gi, off), lam0, lev, ro)
+                # (e) ISP sub-partition number 1 of a CU (TU shape <- CU shape, split): the previous one coded for odd patterns
+                for (tw, th, w, h, isp) in ((1, 16, 4, 16, 2), (16, 1, 16, 4, 1), (2, 8, 8, 8, 2), (8, 2, 8, 8, 1), (4, 16, 16, 16, 2)) if qp in qps_of("e", pat) else ():
+                    off, _, _, resi = inputs(pat, tw, th, bd)
+                    R.ref_env_reset(env)
+                    prev = pat & 1
+                    lev = np.zeros(tw * th, np.int32); ro = np.zeros(tw * th, np.int16); a = C.c_int(); tw_ = C.c_int(); th_ = C.c_int()
+                    assert R.ref_env_trquant_isp(env, 0, 0, w, h, isp, 1, qp, lam0, prev, prev, P(s0), P(s1), P(resi), P(lev), P(ro), C.byref(a), C.byref(tw_), C.byref(th_)) == 0
+                    assert (tw_.value, th_.value) == (tw, th)
+                    keep("e", (bd, qp, w, h, isp, 1, 4, tw, th, prev, 0, a.value, gi, pat, off), lam0, lev, ro)
+            gi += 1
+    out = dict(org=np.concatenate(pool_org), pred=np.concatenate(pool_pred), ctx=np.stack(ctx_all))
+    d_off = sorted(set((m[9], m[2] * m[3]) for m in fam["d"]["meta"]))                # this leaf takes the residual itself: its own pool, indexed like org / pred
+    d_pos = dict(zip([o for (o, _) in d_off], np.concatenate([[0], np.cumsum([n for (_, n) in d_off])])))
+    out["d_resi"] = np.concatenate([(out["org"] - out["pred"])[o:o + n] for (o, n) in d_off]).astype(np.int16)
+    fam["d"]["meta"] = [m[:9] + (int(d_pos[m[9]]),) for m in fam["d"]["meta"]]
+    asum_col = dict(a=6, b=8, c=10, d=7, e=11)
+    for f in "abcde":
+        out[f + "_meta"] = np.asfortranarray(np.array(fam[f]["meta"], np.int32))       # column-major on disk: the columns are long runs, which deflate likes
+        out[f + "_lam"] = np.array(fam[f]["lam"], np.float64)
+        out[f + "_lev"] = np.concatenate(fam[f]["lev"]); out[f + "_resi_out"] = np.concatenate(fam[f]["out"])
+        m = out[f + "_meta"]
+        print("trquant_range (%s): %d cases, non-zero cbf %d (%.1f %%), max abs level %d, max abs reconstructed residual %d" %
+              (f, len(m), int((m[:, asum_col[f]] > 0).sum()), 100.0 * (m[:, asum_col[f]] > 0).mean(), peak[f][0], peak[f][1]) +
+              (", max abs coefficient (oracle forward transform) %d" % cpeak[f] if f in cpeak else ""))
+    np.savez_compressed(os.path.join(HERE, "trquant_range.npz"), **out)
+    print("trquant_range.npz", os.path.getsize(os.path.join(HERE, "trquant_range.npz")), "bytes")
 
 
 def gen_decision_helpers():
@@ -1047,6 +1214,8 @@ if __name__ == "__main__":
     import sys
     if len(sys.argv) > 1 and sys.argv[1] == "decision_helpers2":
         gen_decision_helpers2(); sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "trquant_range":
+        gen_trquant_range(); sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "trquant":
         gen_trquant(); sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "bitstream":
@@ -1099,5 +1268,5 @@ if __name__ == "__main__":
         gen_ts(); sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "cclm":
         gen_cclm(); sys.exit(0)      # added later: leaves the earlier fixtures (and the shared rng stream they used) untouched
-    gen_transforms(); gen_dist(); gen_cabac(); gen_scan(); gen_intra(); gen_partition(); gen_trquant(); gen_bitstream(); gen_cclm(); gen_bitstream_cclm(); gen_trquant_mts(); gen_bitstream_mts(); gen_bitstream_mip(); gen_chroma_qp(); gen_deblock(); gen_mip(); gen_depquant(); gen_bitstream_dq(); gen_lfnst(); gen_bitstream_lfnst(); gen_bitstream_jccr(); gen_ict(); gen_decision_helpers(); gen_ts(); gen_bitstream_ts(); gen_isp(); gen_bitstream_isp(); gen_lmcs(); gen_bitstream_wpp(); gen_lmcs_analysis(); gen_sao(); gen_alf()
+    gen_transforms(); gen_dist(); gen_cabac(); gen_scan(); gen_intra(); gen_partition(); gen_trquant(); gen_bitstream(); gen_cclm(); gen_bitstream_cclm(); gen_trquant_mts(); gen_bitstream_mts(); gen_bitstream_mip(); gen_chroma_qp(); gen_deblock(); gen_mip(); gen_depquant(); gen_bitstream_dq(); gen_lfnst(); gen_bitstream_lfnst(); gen_bitstream_jccr(); gen_ict(); gen_decision_helpers(); gen_ts(); gen_bitstream_ts(); gen_isp(); gen_bitstream_isp(); gen_lmcs(); gen_bitstream_wpp(); gen_lmcs_analysis(); gen_sao(); gen_alf(); gen_trquant_range()
     print("done")

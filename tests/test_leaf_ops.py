@@ -205,6 +205,140 @@ def _isp_tu(lib, limit):
     return n
 
 
+# ---- full-range residuals (tests/golden/trquant_range.npz): the fixture's own org and pred, so that org - pred spans +-(2^bd - 1) ----
+def _range_slice(fam, limit):
+    """every case of a family, or (CPU emulation) limit blocks of at most 256 samples spread evenly over the patterns, bit depths and QPs"""
+    from test_oracle_golden import _range_cases
+    cases = _range_cases(fam)
+    if not limit:
+        return cases
+    small = [c for c in cases if c["w"] * c["h"] <= 256]
+    return small[::max(1, len(small) // limit)][:limit]
+
+
+def _range_expect(c, lev, rec, sse, cbf, key):
+    """block results of a leaf call against the reference: levels, cbf, rec == clip(pred + resi_out) if coded else pred, SSE(org, rec)"""
+    mx = (1 << c["bd"]) - 1
+    assert np.array_equal(lev.ravel(), c["lev"]) and int(cbf) == int(c["asum"] > 0), ("levels", key)
+    rec_e = np.clip(c["pred"].astype(np.int32) + c["out"], 0, mx) if c["asum"] > 0 else c["pred"].astype(np.int32)
+    assert np.array_equal(rec.ravel().astype(np.int32), rec_e), ("rec", key)
+    assert int(sse) == int(((c["org"].astype(np.int64) - rec_e) ** 2).sum()), ("sse", key)
+
+
+def _range_trquant(lib, limit):
+    n = 0
+    for c in _range_slice("a", limit):
+        lev, rec, sse, cbf = pkg.transform_quant_batch(c["org"], c["pred"], c["w"], c["h"], c["bd"], c["qp"] + 6 * (c["bd"] - 8), lib_path=lib)
+        _range_expect(c, lev, rec, sse[0], cbf[0], ("a", c["bd"], c["qp"], c["w"], c["h"], c["pat"]))
+        n += 1
+    return n
+
+
+def _range_depquant(lib, limit):
+    n = 0
+    for c in _range_slice("b", limit):
+        lev, rec, sse, cbf = pkg.depquant_batch(c["org"], c["pred"], c["w"], c["h"], c["bd"], c["qp_used"], c["comp"], c["mts"], c["cbf_cb"], c["lam"], c["ctx"][0], c["ctx"][1], lib_path=lib)
+        _range_expect(c, lev, rec, sse[0], cbf[0], ("b", c["bd"], c["qp"], c["comp"], c["w"], c["h"], c["mts"], c["cbf_cb"], c["pat"]))
+        n += 1
+    return n
+
+
+def _range_lfnst(lib, limit):
+    n = 0
+    for c in _range_slice("c", limit):
+        lev, rec, sse, cbf = pkg.lfnst_depquant_batch(c["org"], c["pred"], c["w"], c["h"], c["bd"], c["qp_used"], c["comp"], c["lfnst"], c["dir"], c["cbf_cb"], c["lam"], c["ctx"][0], c["ctx"][1], lib_path=lib)
+        _range_expect(c, lev, rec, sse[0], cbf[0], ("c", c["bd"], c["qp"], c["w"], c["h"], c["dir"], c["lfnst"], c["pat"]))
+        n += 1
+    return n
+
+
+def _range_transform_skip(lib, limit):
+    vv = importlib.import_module(PKGNAME + ".vvcx")
+    n = 0
+    for c in _range_slice("d", limit):
+        s0, s1 = c["ctx"]
+        l, o, aa, kk, bits = vv.transform_skip_batch(c["resi"], c["w"], c["h"], c["bd"], c["qp"] + 6 * (c["bd"] - 8), c["lam"], s0, s1, lib_path=lib)
+        key = ("d", c["bd"], c["qp"], c["w"], c["h"], c["pat"])
+        assert np.array_equal(l.ravel(), c["lev"]) and int(aa[0]) == c["asum"], ("levels", key)
+        assert int(kk[0]) == c["keep"], ("pruning", key)
+        if c["asum"] > 0:
+            assert np.array_equal(o.ravel(), c["out"]), ("residual", key)
+        n += 1
+    return n
+
+
+def _range_isp_tu(lib, limit):
+    vv = importlib.import_module(PKGNAME + ".vvcx")
+    n = 0
+    for c in _range_slice("e", limit):
+        s0, s1 = c["ctx"]
+        l, r, sse, cbf = vv.isp_tu_batch(c["org"], c["pred"], c["w"], c["h"], c["bd"], c["qp"] + 6 * (c["bd"] - 8), c["lam"], c["prev"], c["inferred"], s0, s1, lib_path=lib)
+        _range_expect(c, l, r, sse[0], cbf[0], ("e", c["bd"], c["qp"], c["w"], c["h"], c["isp"], c["prev"], c["pat"]))
+        n += 1
+    return n
+
+
+def _range_batched(lib, shapes):
+    """all patterns of one (shape, bit depth, QP) back to back in one launch of the plain and one of the dependent quantiser: block i (workgroup i with its own slice of the
+    transform scratch, 2048 int32 that a 64x64 block fills to the last word, and of the trellis scratch) must equal the reference's case i"""
+    from test_oracle_golden import _range_cases
+    n = 0
+    for fam in "ab":
+        groups = {}
+        for c in _range_cases(fam):
+            if (c["w"], c["h"]) in shapes and c.get("comp", 0) == 0 and c.get("mts", 0) == 0:
+                groups.setdefault((c["w"], c["h"], c["bd"], c["qp"]), []).append(c)
+        assert len(groups) == len(shapes) * 6
+        for (w, h, bd, qp), cs in groups.items():
+            assert len(cs) == (11 if qp == 27 else 9) and len(set(c["pat"] for c in cs)) == len(cs)
+            org = np.concatenate([c["org"] for c in cs]); pred = np.concatenate([c["pred"] for c in cs])
+            if fam == "a":
+                lev, rec, sse, cbf = pkg.transform_quant_batch(org, pred, w, h, bd, qp + 6 * (bd - 8), lib_path=lib)
+            else:
+                c0 = cs[0]
+                assert all((c["qp_used"], c["lam"], c["gi"]) == (c0["qp_used"], c0["lam"], c0["gi"]) for c in cs)
+                lev, rec, sse, cbf = pkg.depquant_batch(org, pred, w, h, bd, c0["qp_used"], 0, 0, 0, c0["lam"], c0["ctx"][0], c0["ctx"][1], lib_path=lib)
+            for i, c in enumerate(cs):
+                _range_expect(c, lev[i], rec[i], sse[i], cbf[i], ("batch", fam, i, bd, qp, w, h, c["pat"]))
+                n += 1
+    return n
+
+
+@pytest.mark.gpu
+def test_gpu_full_range_transform_quant_matches_reference():
+    """incl. the matrix-core rows of 32- and 64-wide blocks, which only the GPU build has: high bytes -4 .. 3 of the operand split, idle half tiles (32x4, 64x8), two tiles (32x64)"""
+    assert _range_trquant(None, None) == 580
+
+
+@pytest.mark.gpu
+def test_gpu_full_range_dependent_quantisation_matches_reference():
+    assert _range_depquant(None, None) == 1276
+
+
+@pytest.mark.gpu
+def test_gpu_full_range_lfnst_matches_reference():
+    assert _range_lfnst(None, None) == 432
+
+
+@pytest.mark.gpu
+def test_gpu_full_range_transform_skip_matches_reference():
+    assert _range_transform_skip(None, None) == 232
+
+
+@pytest.mark.gpu
+def test_gpu_full_range_isp_sub_partition_blocks_match_reference():
+    assert _range_isp_tu(None, None) == 290
+
+
+@pytest.mark.gpu
+def test_gpu_batched_leaf_launches_match_reference_block_by_block():
+    assert _range_batched(None, ((4, 4), (32, 4), (32, 32), (64, 64))) == 2 * 4 * (2 * 9 + 11) * 2
+
+
+def test_emulated_batched_leaf_launches_match_reference_block_by_block(emu_so):
+    assert _range_batched(emu_so, ((4, 4), (32, 4))) == 2 * 2 * (2 * 9 + 11) * 2
+
+
 @pytest.mark.gpu
 def test_gpu_isp_sub_partition_blocks_match_reference():
     assert _isp_tu(None, None) == 624
@@ -256,6 +390,11 @@ def test_emulated_leaf_operators_match_reference(emu_so):
     assert _lfnst(emu_so, 16) == 16
     assert _transform_skip(emu_so, 40) == 40
     assert _isp_tu(emu_so, 30) == 30
+    assert _range_trquant(emu_so, 32) == 32                 # full-range residuals: slices of tests/golden/trquant_range.npz
+    assert _range_depquant(emu_so, 32) == 32
+    assert _range_lfnst(emu_so, 24) == 24
+    assert _range_transform_skip(emu_so, 24) == 24
+    assert _range_isp_tu(emu_so, 24) == 24
 
 
 @pytest.mark.gpu

@@ -738,3 +738,157 @@ def test_cu_and_tu_level_predicates_against_commonlib():
         assert itype == (7, 8, 9)[isp] and prd == int(isp == 2 and minw)            # TU_NO_ISP / TU_1D_HORZ_SPLIT / TU_1D_VERT_SPLIT; the 4-column regions only for vertical splits
         assert dual == 1 and tsC == 0 and mtsC == 0 and nlm == 3 and [int(v) for v in r[15:18]] == [67, 68, 69]
     L.orc_destroy(e)
+
+
+# ---- the transform / quantiser leaves at the full range of org - pred (tests/golden/trquant_range.npz, make_golden.py gen_trquant_range) ----
+_RANGE_COLS = dict(a=("bd", "qp", "w", "h", "pat", "in_off", "asum"),
+                   b=("bd", "qp", "comp", "w", "h", "mts", "cbf_cb", "qp_used", "asum", "gi", "pat", "in_off"),
+                   c=("bd", "qp", "comp", "w", "h", "dir", "mip", "lfnst", "dq", "cbf_cb", "asum", "gi", "qp_used", "pat", "in_off"),
+                   d=("bd", "qp", "w", "h", "pat", "keep", "qp_used", "asum", "gi", "in_off"),
+                   e=("bd", "qp", "cuw", "cuh", "isp", "tu", "n", "w", "h", "prev", "inferred", "asum", "gi", "pat", "in_off"))
+_RANGE_COUNT = dict(a=580, b=1276, c=432, d=232, e=290)
+_range_cache = {}
+
+
+def _range_cases(fam):
+    """cases of one family of trquant_range.npz: the meta columns by name, org / pred (the transform-skip family: resi alone), resi = org - pred, the reference's
+    levels (lev), reconstructed residual (out) and absSum (asum); w x h is the block the leaf codes.  Read once, shared by the CPU and GPU tests, never written to."""
+    if fam not in _range_cache:
+        z = np.load(os.path.join(G, "trquant_range.npz"), allow_pickle=False)
+        g = {k: z[k] for k in ("org", "pred", "ctx", "d_resi") + tuple(fam + s for s in ("_meta", "_lam", "_lev", "_resi_out"))}
+        cases, off = [], 0
+        for k, row in enumerate(g[fam + "_meta"]):
+            c = dict(zip(_RANGE_COLS[fam], (int(v) for v in row)))
+            n = c["w"] * c["h"]; i = c["in_off"]
+            if fam == "d":
+                c["resi"] = np.ascontiguousarray(g["d_resi"][i:i + n])
+            else:
+                c["org"] = g["org"][i:i + n]; c["pred"] = g["pred"][i:i + n]
+                c["resi"] = np.ascontiguousarray(c["org"] - c["pred"])
+            c["lam"] = float(g[fam + "_lam"][k]); c["lev"] = g[fam + "_lev"][off:off + n]; c["out"] = g[fam + "_resi_out"][off:off + n]
+            if "gi" in c: c["ctx"] = g["ctx"][c["gi"]]
+            for v in c.values():
+                if isinstance(v, np.ndarray): v.flags.writeable = False
+            cases.append(c); off += n
+        assert off == len(g[fam + "_lev"]) == len(g[fam + "_resi_out"])
+        _range_cache[fam] = cases
+    return _range_cache[fam]
+
+
+def _range_properties(fam):
+    """what makes the fixture worth having: the exact case count, the residual of every (shape, bit depth) reaches both -(2^bd - 1) and 2^bd - 1, the 10-bit residuals of some
+    32- or 64-wide block take every high byte -4 .. 3 (the operand split of the device's matrix-core rows), and at least half of the cases are coded"""
+    cases = _range_cases(fam)
+    assert len(cases) == _RANGE_COUNT[fam]
+    lo, hi, high_bytes = {}, {}, {}
+    for c in cases:
+        key = (c["w"], c["h"], c["bd"]); r = c["resi"].astype(np.int32)
+        lo[key] = min(lo.get(key, 0), int(r.min())); hi[key] = max(hi.get(key, 0), int(r.max()))
+        if c["bd"] == 10 and c["w"] >= 32: high_bytes.setdefault(key, set()).update(np.unique(r >> 8).tolist())
+    for (w, h, bd) in lo:
+        assert lo[(w, h, bd)] == -((1 << bd) - 1) and hi[(w, h, bd)] == (1 << bd) - 1, ("range", fam, w, h, bd)
+    if fam in "abd":                                       # the families with 32- / 64-wide blocks under random patterns
+        assert any(s == set(range(-4, 4)) for s in high_bytes.values()), ("high bytes", fam, high_bytes)
+    assert 2 * sum(c["asum"] > 0 for c in cases) >= len(cases), ("coded share", fam)
+    return cases
+
+
+def test_full_range_transform_quant_round_trip():
+    """(a) DCT-II + plain quantiser + dequantiser + inverse at residuals of +-(2^bd - 1): flat, checkerboard, stripes, step edges, impulses, the sign pattern of the last row the
+    zero-out keeps, uniform and two-valued noise; slice QP 4 / 27 / 51; 8 / 10 bit; 4x4 .. 64x64 == TrQuant::transformNxN / invTransformNxN of the reference"""
+    L = O.lib()
+    peak = 0
+    for c in _range_properties("a"):
+        w, h, bd, k = c["w"], c["h"], c["bd"], c["w"] * c["h"]
+        q = c["qp"] + 6 * (bd - 8)
+        coef = np.zeros(k, np.int32); lev = np.zeros(k, np.int16)
+        L.orc_fwd_2d(P(c["resi"]), w, w, h, bd, P(coef))
+        peak = max(peak, int(np.abs(coef).max()))
+        key = (bd, c["qp"], w, h, c["pat"])
+        assert L.orc_quant(P(coef), w, h, bd, q, P(lev)) == c["asum"], ("abs_sum", key)
+        assert np.array_equal(lev, c["lev"]), ("levels", key)
+        if c["asum"] > 0:
+            dq = np.zeros(k, np.int32); out = np.zeros(k, np.int16)
+            L.orc_dequant(P(lev), w, h, bd, q, P(dq)); L.orc_inv_2d(P(dq), w, h, bd, P(out), w)
+            assert np.array_equal(out, c["out"]), ("resi", key)
+    assert peak == 32736                                   # DC of a flat +-1023 residual on 64x64: the largest coefficient legal input reaches stays inside 16 bits
+
+
+def test_full_range_dependent_quantisation_against_the_reference_trellis():
+    """(b) DepQuant at residuals of +-(2^bd - 1): the luma shapes of (a), explicit MTS 2 .. 5 on 16x16 / 32x32, Cb 2x8 / 8x2, Cr 4x4 with both values of cbf_cb"""
+    L = O.lib()
+    L.orc_depquant.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_double, C.c_int, C.c_int, C.c_void_p]
+    cbf_base = (72, 76, 77)                           # ORC_CTX_QtCbf
+    seen = set()
+    for c in _range_properties("b"):
+        w, h, bd, comp, n = c["w"], c["h"], c["bd"], c["comp"], c["w"] * c["h"]
+        coef = np.zeros(n, np.int32); lev = np.zeros(n, np.int16); out = np.zeros(n, np.int16)
+        L.orc_fwd_2d_mts(P(c["resi"]), w, w, h, bd, c["mts"], P(coef))
+        assert np.abs(coef).max() <= 32767            # what the device narrows to int16 in front of its trellis
+        s0 = np.ascontiguousarray(c["ctx"][0]); s1 = np.ascontiguousarray(c["ctx"][1])
+        cbf_ctx = cbf_base[comp] + (1 if comp == 2 and c["cbf_cb"] else 0)
+        a = L.orc_depquant(P(s0), P(s1), P(coef), w, h, comp, cbf_ctx, bd, c["qp_used"], c["lam"], 1 if c["mts"] > 1 else 0, 0, P(lev))
+        key = (bd, c["qp"], comp, w, h, c["mts"], c["cbf_cb"], c["pat"])
+        assert a == c["asum"], ("absSum", key, a, c["asum"])
+        assert np.array_equal(lev, c["lev"]), ("levels", key)
+        if a:
+            L.orc_dequant_dq(P(lev), w, h, bd, c["qp_used"], P(coef))
+            L.orc_inv_2d_mts(P(coef), w, h, bd, c["mts"], P(out), w)
+            assert np.array_equal(out, c["out"]), ("resi", key)
+        seen.add((comp, w, h, c["mts"], c["cbf_cb"]))
+    assert len(seen) == 10 + 8 + 4
+
+
+def test_full_range_lfnst_against_the_reference_transform_path():
+    """(c) LFNST 1 / 2 over DepQuant at residuals of +-(2^bd - 1): 4x4 .. 32x32, the nine structured patterns, intra modes 0 / 1 / 34 / 66 rotating over them"""
+    L = O.lib()
+    L.orc_trquant_lfnst.argtypes = [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_double] + [C.c_int] * 3 + [C.c_void_p] * 2
+    seen = set()
+    for c in _range_properties("c"):
+        w, h, n = c["w"], c["h"], c["w"] * c["h"]
+        lev = np.zeros(n, np.int16); out = np.zeros(n, np.int16)
+        s0 = np.ascontiguousarray(c["ctx"][0]); s1 = np.ascontiguousarray(c["ctx"][1])
+        a = L.orc_trquant_lfnst(P(s0), P(s1), P(c["resi"]), w, h, c["comp"], c["cbf_cb"], c["bd"], c["qp_used"], c["lam"], c["dq"], c["dir"], c["lfnst"], P(lev), P(out))
+        key = (c["bd"], c["qp"], w, h, c["dir"], c["lfnst"], c["pat"])
+        assert a == c["asum"], ("absSum", key, a, c["asum"])
+        assert np.array_equal(lev, c["lev"]), ("levels", key)
+        if a:
+            assert np.array_equal(out, c["out"]), ("resi", key)
+        seen.add((w, c["lfnst"], c["dir"]))
+    assert len(seen) == 4 * 2 * 4                          # every direction meets every shape and index
+
+
+def test_full_range_transform_skip_against_the_reference_rdoq_ts():
+    """(d) transform skip with RDOQ-TS on bare residuals of +-(2^bd - 1): 4x4, 8x8, 32x4, 32x32"""
+    L = O.lib()
+    L.orc_trquant_ts.argtypes = [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_double] + [C.c_void_p] * 3
+    for c in _range_properties("d"):
+        w, h, n = c["w"], c["h"], c["w"] * c["h"]
+        lev = np.zeros(n, np.int16); out = np.zeros(n, np.int16); keep = C.c_int()
+        s0 = np.ascontiguousarray(c["ctx"][0]); s1 = np.ascontiguousarray(c["ctx"][1])
+        qp_prime = c["qp"] + 6 * (c["bd"] - 8)
+        a = L.orc_trquant_ts(P(s0), P(s1), P(c["resi"]), w, h, c["bd"], qp_prime, c["lam"], P(lev), P(out), C.byref(keep))
+        key = (c["bd"], c["qp"], w, h, c["pat"])
+        assert max(qp_prime, 4) == c["qp_used"], key
+        assert keep.value == c["keep"], ("pruning", key)
+        assert a == c["asum"], ("absSum", key, a, c["asum"])
+        assert np.array_equal(lev, c["lev"]), ("levels", key)
+        if a:
+            assert np.array_equal(out, c["out"]), ("resi", key)
+
+
+def test_full_range_isp_sub_partition_transform_path_against_the_reference():
+    """(e) ISP sub-partition blocks 1x16, 16x1, 2x8, 8x2, 4x16 at residuals of +-(2^bd - 1), the previous sub-partition coded or not"""
+    L = O.lib()
+    L.orc_trquant_isp.argtypes = [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_double, C.c_int] + [C.c_void_p] * 2
+    for c in _range_properties("e"):
+        n = c["w"] * c["h"]
+        lev = np.zeros(n, np.int16); out = np.zeros(n, np.int16)
+        s0 = np.ascontiguousarray(c["ctx"][0]); s1 = np.ascontiguousarray(c["ctx"][1])
+        cbf_ctx = -1 if c["inferred"] else 72 + 2 + c["prev"]                 # ORC_CTX_QtCbf[0] + 2 + the previous sub-partition's cbf
+        a = L.orc_trquant_isp(P(s0), P(s1), P(c["resi"]), c["w"], c["h"], c["bd"], c["qp"] + 6 * (c["bd"] - 8), c["lam"], cbf_ctx, P(lev), P(out))
+        key = (c["bd"], c["qp"], c["w"], c["h"], c["isp"], c["prev"], c["pat"])
+        assert a == c["asum"], ("absSum", key, a, c["asum"])
+        assert np.array_equal(lev, c["lev"]), ("levels", key)
+        if a:
+            assert np.array_equal(out, c["out"]), ("resi", key)
