@@ -1606,45 +1606,6 @@ __device__ __noinline__ void wave_sad_satd(const int16_t *org_g, const int16_t *
   satd_out = (unsigned long long) (unsigned) wave_sum_i32(b);
 }
 
-// ------------------------------------------------------------------------------------------------ transform + quant (one wave)
-// four matrix coefficients (int8, one 32-bit load) times four int16 samples (one 64-bit load) / four int32 values (one 128-bit load):
-// rows of the matrices and of the sample tiles start at multiples of their length (>= 4 elements) in 16-byte aligned buffers
-struct alignas(16) I32x4 { int x, y, z, w; };
-// The first transform stage multiplies int8 matrix rows with 16-bit samples: two packed dot products (v_dot2c_i32_i16: two int16 x int16 products accumulated into 32
-// bits, exact) per four samples; the residual pair comes from one packed subtraction (v_pk_sub_i16; samples and predictions are below 2^15).
-#ifndef VX_DOT2_I16
-typedef short vx_s2 __attribute__((ext_vector_type(2)));
-#define VX_DOT2_I16(a_, b_, c_) __builtin_amdgcn_sdot2(__builtin_bit_cast(vx_s2, (uint32_t) (a_)), __builtin_bit_cast(vx_s2, (uint32_t) (b_)), (c_), false)
-#define VX_PKSUB_I16(a_, b_) __builtin_bit_cast(uint32_t, __builtin_bit_cast(vx_s2, (uint32_t) (a_)) - __builtin_bit_cast(vx_s2, (uint32_t) (b_)))
-#endif
-__device__ inline uint2 m8x4_to_16(uint32_t m)                    // four int8 coefficients -> two words of packed int16 pairs
-{
-  uint2 r;
-  r.x = (uint32_t) (uint16_t) (int16_t) (int8_t) m | ((uint32_t) (int) (int8_t) (m >> 8) << 16);
-  r.y = (uint32_t) (uint16_t) (int16_t) (int8_t) (m >> 16) | ((uint32_t) ((int) m >> 24) << 16);
-  return r;
-}
-__device__ inline int dot4_s16(uint32_t m, uint2 d)
-{
-  const uint2 c = m8x4_to_16(m);
-  return VX_DOT2_I16(c.y, d.y, VX_DOT2_I16(c.x, d.x, 0));
-}
-__device__ inline int dot4_resi(uint32_t m, uint2 a, uint2 b)     // coefficients times (a - b), element-wise int16
-{
-  const uint2 c = m8x4_to_16(m);
-  return VX_DOT2_I16(c.y, VX_PKSUB_I16(a.y, b.y), VX_DOT2_I16(c.x, VX_PKSUB_I16(a.x, b.x), 0));
-}
-__device__ inline int dot4_s32(uint32_t m, I32x4 d)
-{
-  return (int) (int8_t) m * d.x + (int) (int8_t) (m >> 8) * d.y + (int) (int8_t) (m >> 16) * d.z + (int) (int8_t) (m >> 24) * d.w;
-}
-// the same with the four data elements taken in reverse order (DCT-VIII rows are DST-VII rows on the reversed input)
-__device__ inline uint2 rev4_s16(uint2 d) { uint2 r; r.x = (d.y >> 16) | (d.y << 16); r.y = (d.x >> 16) | (d.x << 16); return r; }
-__device__ inline I32x4 rev4_s32(I32x4 d) { I32x4 r; r.x = d.w; r.y = d.z; r.z = d.y; r.w = d.x; return r; }
-template <bool SMALL> __device__ inline const int8_t *dct2_matrix(int n)
-{
-  switch (n) { case 2: return VX_DCT2_2; case 4: return VX_DCT2_4; case 8: return VX_DCT2_8; case 16: return VX_DCT2_16; case 32: return VX_DCT2_32; default: return VX_DCT2_64; }
-}
 __device__ void load_tables()
 {
   const int tid = VTX;
@@ -1727,446 +1688,8 @@ __device__ __noinline__ void lmcs_chroma_adj(int nx, int ny)
   __threadfence_block();
   __syncthreads();
 }
-// residual (org - pred) → DCT-II (TrQuant::xT 835-915) → plain quant (Quant::quant 994-1089) → levels;
-// if any level: dequant (423-549) → inverse DCT-II (xIT 917-992) → reco = clip(pred + resi) written over pred.
-// Returns SSE(org, reco) and abs-sum via out params.  rec/lev tiles have stride w.
-// given >= 0: the levels in lev are taken as coded (cbf = given): only the decoder half runs (DecCu::xIntraRecBlk, DL/DecCu.cpp:199-414).
-// SMALL: rec / lev / tmp are the calling wave's LDS buffers (L.wm[wave].slot + buf_off, + 1024, L.wm[wave].tmp); else the _g pointers.
-// With VVCX_TOOL_DEPQUANT the quantiser is the trellis of wave_depquant (comp: 0 Y / 1 Cb / 2 Cr, ci: the context set its rate terms are read from =
-// the estimator's contexts at this point of the search, cbf_cb: tu.cbf[Cb] when Cr is quantised) and the dequantiser its state machine.
-template <bool SMALL, bool SUMABS = false>
-__device__ __noinline__ void wave_code_block(const int16_t *org_g, int org_off, int buf_off, int16_t *rec_g, int16_t *lev_g, int32_t *tmp_g, int w, int h, int bd, int qp,
-                                int lane, unsigned long long &sse_out, int &cbf_out, int given = -1, int *sumabs_out = nullptr, int comp = 0, int ci = 0, int cbf_cb = 0,
-                                int lf = 0, int lfmode = 0, int raw = 0, int qidx = -1, int cadj = 0)
-{
-  org_g = uni_p(org_g); rec_g = uni_p(rec_g); lev_g = uni_p(lev_g); tmp_g = uni_p(tmp_g); sumabs_out = uni_p(sumabs_out);      // uniform arguments arrive in vector registers: scalar from here on
-  // cadj: LMCS chroma residual scale of the block (0: none): the residual is divided by it in front of the transform and multiplied back behind the inverse
-  // raw: the block is a bare residual (org = the residual, rec = zeros on entry): rec receives the reconstructed residual, unclipped (joint chroma blocks)
-  // lf: cu.lfnstIdx for a block of at least 4x4 (0 otherwise), lfmode: lfnst_mode() of its final intra mode (dependent quantisation only)
-  int coef_sum = 0;                                     // SUMABS: sum of |DCT-II coefficient| for the MTS pruning (TrQuant::transformNxN 1049-1124)
-  w = uni(w); h = uni(h); bd = uni(bd); qp = uni(qp); given = uni(given);
-  const int dq = uni((int) (L.par.tools & TOOL_DEPQUANT)) != 0;
-  const int wave_ = uni(VTX >> 6);
-  const int16_t *org = (SMALL ? L.org : org_g) + uni(org_off);
-  int16_t *rec = SMALL ? L.wm[wave_].slot + uni(buf_off) : rec_g, *lev = SMALL ? L.wm[wave_].slot + BUF + uni(buf_off) : lev_g;
-  int32_t *tmp = SMALL ? L.wm[wave_].tmp : tmp_g;
-  const int P = w * h, lw = ilog2i(w), lh = ilog2i(h);
-  const int zw = imin(w, 32), zh = imin(h, 32), lzw = imin(lw, 5);
-  lf = uni(lf); lfmode = uni(lfmode);
-  const int lfsb = (w >= 8 && h >= 8) ? 8 : 4;            // with LFNST only the top-left 4x4 / 8x8 of the primary coefficients is kept (xT 855-868)
-  const int fzw = lf ? lfsb : zw, fzh = lf ? lfsb : zh, lfzw = lf ? ilog2i(lfsb) : lzw;
-  const int8_t *Mw = dct2_matrix<SMALL>(w), *Mh = dct2_matrix<SMALL>(h);
-  const int shift1 = lw + bd + 6 - 15, shift2 = lh + 6;
-  const int rnd1 = shift1 > 0 ? 1 << (shift1 - 1) : 0, rnd2 = 1 << (shift2 - 1);
-  cadj = uni(cadj);
-  if (cadj && given < 0) {                              // the scaled residual passes through the (still unused) level buffer
-    for (int o = lane; o < P; o += 64) lev[o] = (int16_t) lmcs_scale_fwd(org[o] - rec[o], cadj, bd);
-    wave_sync();
-  }
-  // stage 1 (horizontal): tmp[k*h + j] = (sum_i Mw[k][i] * resi[j][i] + rnd) >> shift1, k < zw
-#ifndef VX_NO_MFMA
-  // 32- and 64-point rows on the matrix cores: D[k][j] = sum_i Mw[k][i] * resi[j][i] is a 32 x w by w x h GEMM of an int8 matrix with 11-bit residuals.  The residual is
-  // split into a signed high byte and an unsigned low byte; the low byte is re-centred (lo - 128, so that it is an int8) and the 128 * (row sum of Mw) it leaves out is added back:
-  // the DCT-II rows sum to zero except row 0 (64 * w; tests/test_host_cpu.py checks the tables).  v_mfma_i32_32x32x16_i8: lane l feeds row l % 32 of A / column l % 32 of B
-  // with the eight k of half l / 32; the 16 results of a lane are rows 8 * (r / 4) + 4 * (l / 32) + r % 4 of column l % 32.  Exact: all partial sums stay far below 2^31.
-  if (!SMALL && given < 0 && !cadj && !lf && (w == 32 || w == 64)) {
-    typedef int vx_i16 __attribute__((ext_vector_type(16)));
-    const int col = lane & 31, half = lane >> 5;
-    for (int jt = 0; jt < h; jt += 32) {
-      vx_i16 accH = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 }, accL = accH;
-      const int j = jt + col;
-      for (int q = 0; q < w; q += 16) {
-        const int i0 = q + half * 8;
-        const uint32_t a0 = *(const uint32_t *) (Mw + col * w + i0), a1 = *(const uint32_t *) (Mw + col * w + i0 + 4);
-        const long a = (long) (((unsigned long long) a1 << 32) | a0);
-        unsigned long long bh = 0, bl = 0;
-        if (j < h) {
-#pragma unroll
-          for (int e = 0; e < 8; e++) {
-            const int r = org[j * w + i0 + e] - rec[j * w + i0 + e];
-            bh |= (unsigned long long) (unsigned) ((r >> 8) & 255) << (8 * e);
-            bl |= (unsigned long long) (unsigned) (((r & 255) - 128) & 255) << (8 * e);
-          }
-        }
-        accH = __builtin_amdgcn_mfma_i32_32x32x16_i8(a, (long) bh, accH, 0, 0, 0);
-        accL = __builtin_amdgcn_mfma_i32_32x32x16_i8(a, (long) bl, accL, 0, 0, 0);
-      }
-      if (j < h) {
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-          const int k = 8 * (r >> 2) + 4 * half + (r & 3);
-          const int sacc = 256 * accH[r] + accL[r] + (k == 0 ? 128 * 64 * w : 0);
-          tmp[k * h + j] = (sacc + rnd1) >> shift1;
-        }
-      }
-    }
-  } else
-#endif
-  if (given < 0) for (int o = lane; o < fzw * h; o += 64) {
-    const int k = o >> lh, j = o & (h - 1);
-    int s = 0;
-    if (cadj) { if (w >= 4) for (int i = 0; i < w; i += 4) s += dot4_s16(*(const uint32_t *) (Mw + k * w + i), *(const uint2 *) (lev + j * w + i)); else for (int i = 0; i < w; i++) s += Mw[k * w + i] * lev[j * w + i]; }
-    else if (w >= 4) for (int i = 0; i < w; i += 4) s += dot4_resi(*(const uint32_t *) (Mw + k * w + i), *(const uint2 *) (org + j * w + i), *(const uint2 *) (rec + j * w + i));
-    else for (int i = 0; i < w; i++) s += Mw[k * w + i] * (org[j * w + i] - rec[j * w + i]);
-    tmp[o] = (s + rnd1) >> shift1;
-  }
-  wave_sync();
-  // quant parameters
-  const int need_sqrt = (lw + lh) & 1;
-  const int qscale = L.t.qscale[need_sqrt * 6 + qp % 6];
-  const int tr_shift = 15 - bd - ((lw + lh) >> 1) + (need_sqrt ? -1 : 0);
-  const int qbits = 14 + qp / 6 + tr_shift;
-  const long long qadd = (long long) 171 << (qbits - 9);
-  // stage 2 (vertical) + quant: coef[m*w + k], m < zh, k < zw
-  if (given < 0 && (w > 32 || h > 32)) { for (int o = lane; o < P; o += 64) lev[o] = 0; wave_sync(); }
-  int abs_sum = 0;
-  if (given < 0) for (int o = lane; o < fzw * fzh; o += 64) {
-    const int m = o >> lfzw, k = o & (fzw - 1);
-    int s = 0;
-    if (h >= 4) for (int j = 0; j < h; j += 4) s += dot4_s32(*(const uint32_t *) (Mh + m * h + j), *(const I32x4 *) (tmp + k * h + j));
-    else for (int j = 0; j < h; j++) s += Mh[m * h + j] * tmp[k * h + j];
-    const int c = (s + rnd2) >> shift2;
-    if (SUMABS) coef_sum += iabs(c);
-    if (dq) { lev[m * w + k] = (int16_t) c; continue; }       // the trellis works on the coefficients (15 bits + sign by construction of the transform shifts)
-    const long long t = (long long) iabs(c) * qscale;
-    int q = (int) ((t + qadd) >> qbits);
-    abs_sum += q;
-    if (c < 0) q = -q;
-    q = q < -32768 ? -32768 : q > 32767 ? 32767 : q;
-    lev[m * w + k] = (int16_t) q;
-  }
-  if (lf && given < 0) { wave_sync(); wave_lfnst_fwd(lev, w, w, h, lfmode, lf, (int32_t *) &L.wm[wave_].ws, lane); }      // xFwdLfnst (TrQuant::transformNxN 1220-1223)
-  if (given == -2) {                                    // forward half only (batched full-RD stage): the coefficients stay in lev for the trellis of the batch
-    if (SUMABS) *sumabs_out = wave_sum_i32(coef_sum);
-    wave_sync();
-    sse_out = 0; cbf_out = 0;
-    return;
-  }
-  if (dq && given < 0) {
-    wave_sync();
-    abs_sum = wave_depquant<SMALL>(lev, buf_off, L.par.scratch + (size_t) blockIdx.x * L.par.scratch_per_stream, ci, w, h, comp, VX_CTX_QtCbf[comp] + (comp == 2 ? cbf_cb : 0), 0, lf, lane, qidx);
-  } else abs_sum = given < 0 ? uni(wave_sum_i32(abs_sum)) : given;
-  if (SUMABS) *sumabs_out = wave_sum_i32(coef_sum);
-  wave_sync();
-  unsigned long long sse = 0;
-  if (abs_sum > 0) {
-    const int iscale = L.t.iqscale[need_sqrt * 6 + qp % 6];
-    const int right_shift = 6 - (tr_shift + qp / 6);
-    int tbd = 32 + right_shift - 7; if (tbd > 16) tbd = 16;
-    const int in_min = -(1 << (tbd - 1)), in_max = (1 << (tbd - 1)) - 1;
-    // dequantised coefficients once (they are clipped to 16 bits, Quant::dequant 423-549): deq[m*zw + k], int16 at the start of tmp,
-    // followed by the (16-bit clipped) output of the vertical stage: zw*zh + zw*h int16 <= the zw*h int32 the forward pass used
-    int16_t *deq = (int16_t *) tmp, *tcol = deq + zw * zh;
-    if (dq) { wave_dequant_dq(lev, deq, w, h, zw, zh, bd, qp, lane); if (lf) wave_lfnst_inv(deq, zw, w, h, lfmode, lf, (int32_t *) &L.wm[wave_].ws, lane); }      // xInvLfnst (invTransformNxN 593-596)
-    else {
-    for (int o = lane; o < zw * zh; o += 64) {
-      const int m = o >> lzw, k = o & (zw - 1);
-      int q = lev[m * w + k]; q = q < in_min ? in_min : q > in_max ? in_max : q;
-      int v = right_shift > 0 ? (q * iscale + (1 << (right_shift - 1))) >> right_shift : (q * iscale) << (-right_shift);
-      deq[o] = (int16_t) (v < -32768 ? -32768 : v > 32767 ? 32767 : v);
-    }
-    wave_sync();
-    }
-    // inverse stage 1 (vertical): t[j*h + i] = clip((sum_k Mh[k][i] * deq[k][j] + 64) >> 7), j < zw
-    for (int o = lane; o < zw * h; o += 64) {
-      const int j = o >> lh, i = o & (h - 1);
-      int s = 0;
-      for (int k = 0; k < zh; k++) s += Mh[k * h + i] * deq[(k << lzw) + j];
-      int v = (s + 64) >> 7;
-      tcol[o] = (int16_t) (v < -32768 ? -32768 : v > 32767 ? 32767 : v);
-    }
-    wave_sync();
-    const int ishift2 = (6 + 15 - 1) - bd, irnd2 = 1 << (ishift2 - 1);
-    const int mx = (1 << bd) - 1;
-    for (int o = lane; o < P; o += 64) {
-      const int j2 = o >> lw, i2 = o & (w - 1);
-      int s = 0;
-      for (int k = 0; k < zw; k++) s += Mw[k * w + i2] * tcol[k * h + j2];
-      int r = (s + irnd2) >> ishift2;
-      r = r < -32768 ? -32768 : r > 32767 ? 32767 : r;
-      if (raw) { rec[o] = (int16_t) r; continue; }
-      if (cadj) r = lmcs_scale_inv((int) (int16_t) r, cadj, bd);
-      int v = rec[o] + (int) (int16_t) r;
-      v = v < 0 ? 0 : v > mx ? mx : v;
-      rec[o] = (int16_t) v;
-      const int d = org[o] - v;
-      sse += (unsigned long long) (d * d);
-    }
-  } else {
-    for (int o = lane; o < P; o += 64) { const int d = org[o] - rec[o]; sse += (unsigned long long) (d * d); }
-  }
-  wave_sync();
-  sse_out = wave_sum_u64(sse);
-  cbf_out = abs_sum > 0;
-}
-
-// ---- explicit MTS (TrQuant::getTrTypes 817-830): mts_idx 2..5 → (horizontal, vertical) ∈ {DST-VII, DCT-VIII}; tr: 0 DCT2, 1 DCT8, 2 DST7
-__device__ inline void mts_types(int mts, int &trh, int &trv)
-{
-  if (mts < 2) { trh = trv = 0; return; }
-  trh = ((mts - 2) & 1) ? 1 : 2; trv = ((mts - 2) >> 1) ? 1 : 2;
-}
-template <bool SMALL> __device__ inline const int8_t *tr_matrix(int tr, int n)
-{
-  if (tr == 0) return dct2_matrix<SMALL>(n);
-  return n == 4 ? VX_DST7_4 : n == 8 ? VX_DST7_8 : n == 16 ? VX_DST7_16 : VX_DST7_32;
-}
-__device__ inline int tr_coef(const int8_t *M, int n, int tr, int k, int i)
-{
-  if (tr == 1) { const int v = M[k * n + (n - 1 - i)]; return (k & 1) ? -v : v; }
-  return M[k * n + i];
-}
-// forward 2-D transform of (org - pred) with the transform pair of mts and the sum of |coefficient| (the measure TrQuant::transformNxN
-// 1049-1124 prunes the MTS candidates with); pred is the calling wave's candidate buffer (SMALL) or pred_g
-template <bool SMALL>
-__device__ __noinline__ int wave_fwd_sumabs(const int16_t *org_g, const int16_t *pred_g, int32_t *tmp_g, int w, int h, int bd, int mts, int lane)
-{
-  org_g = uni_p(org_g); pred_g = uni_p(pred_g); tmp_g = uni_p(tmp_g);
-  w = uni(w); h = uni(h); bd = uni(bd); mts = uni(mts);
-  const int wave_ = uni(VTX >> 6);
-  const int16_t *org = SMALL ? L.org : org_g, *pred = SMALL ? L.wm[wave_].slot : pred_g;
-  int32_t *tmp = SMALL ? L.wm[wave_].tmp : tmp_g;
-  int trh, trv; mts_types(mts, trh, trv);
-  const int lw = ilog2i(w), lh = ilog2i(h);
-  const int zw = (trh && w == 32) ? 16 : imin(w, 32), zh = (trv && h == 32) ? 16 : imin(h, 32), lzw = ilog2i(zw);
-  const int8_t *Mw = tr_matrix<SMALL>(trh, w), *Mh = tr_matrix<SMALL>(trv, h);
-  const int shift1 = lw + bd + 6 - 15, shift2 = lh + 6;
-  const int rnd1 = shift1 > 0 ? 1 << (shift1 - 1) : 0, rnd2 = 1 << (shift2 - 1);
-  for (int o = lane; o < zw * h; o += 64) {
-    const int k = o >> lh, j = o & (h - 1);
-    int s = 0;
-    // DCT-VIII[k][i] = (-1)^k DST-VII[k][n-1-i]: the DST-VII row applied to the reversed input, sign by the parity of k
-    if (trh == 1) { for (int i = 0; i < w; i += 4) s += dot4_resi(*(const uint32_t *) (Mw + k * w + i), rev4_s16(*(const uint2 *) (org + j * w + w - 4 - i)), rev4_s16(*(const uint2 *) (pred + j * w + w - 4 - i))); if (k & 1) s = -s; }
-    else for (int i = 0; i < w; i += 4) s += dot4_resi(*(const uint32_t *) (Mw + k * w + i), *(const uint2 *) (org + j * w + i), *(const uint2 *) (pred + j * w + i));
-    tmp[o] = (s + rnd1) >> shift1;
-  }
-  wave_sync();
-  int sa = 0;
-  for (int o = lane; o < zw * zh; o += 64) {
-    const int m = o >> lzw, k = o & (zw - 1);
-    int s = 0;
-    if (trv == 1) { for (int j = 0; j < h; j += 4) s += dot4_s32(*(const uint32_t *) (Mh + m * h + j), rev4_s32(*(const I32x4 *) (tmp + k * h + h - 4 - j))); if (m & 1) s = -s; }
-    else for (int j = 0; j < h; j += 4) s += dot4_s32(*(const uint32_t *) (Mh + m * h + j), *(const I32x4 *) (tmp + k * h + j));
-    sa += iabs((s + rnd2) >> shift2);
-  }
-  sa = wave_sum_i32(sa);
-  wave_sync();
-  return sa;
-}
-// wave_code_block with an explicit-MTS transform pair (mts 2..5; blocks up to 32x32): same steps, DST-VII / DCT-VIII matrices, and the
-// 32-point transforms keep 16 coefficients (TrQuant::xT 853-854, xIT 935-936)
-template <bool SMALL>
-__device__ __noinline__ void wave_code_block_mts(const int16_t *org_g, int16_t *rec_g, int16_t *lev_g, int32_t *tmp_g, int w, int h, int bd, int qp, int mts,
-                                                 int lane, unsigned long long &sse_out, int &cbf_out, int given = -1)
-{
-  org_g = uni_p(org_g); rec_g = uni_p(rec_g); lev_g = uni_p(lev_g); tmp_g = uni_p(tmp_g);
-  w = uni(w); h = uni(h); bd = uni(bd); qp = uni(qp); given = uni(given); mts = uni(mts);
-  const int dq = uni((int) (L.par.tools & TOOL_DEPQUANT)) != 0;        // luma only: the rate terms come from the node's start contexts (CI_CUR)
-  const int wave_ = uni(VTX >> 6);
-  const int16_t *org = SMALL ? L.org : org_g;
-  int16_t *rec = SMALL ? L.wm[wave_].slot : rec_g, *lev = SMALL ? L.wm[wave_].slot + BUF : lev_g;
-  int32_t *tmp = SMALL ? L.wm[wave_].tmp : tmp_g;
-  int trh, trv; mts_types(mts, trh, trv);
-  const int P = w * h, lw = ilog2i(w), lh = ilog2i(h);
-  const int zw = (trh && w == 32) ? 16 : w, zh = (trv && h == 32) ? 16 : h, lzw = ilog2i(zw);
-  const int8_t *Mw = tr_matrix<SMALL>(trh, w), *Mh = tr_matrix<SMALL>(trv, h);
-  const int shift1 = lw + bd + 6 - 15, shift2 = lh + 6;
-  const int rnd1 = shift1 > 0 ? 1 << (shift1 - 1) : 0, rnd2 = 1 << (shift2 - 1);
-  if (given < 0) for (int o = lane; o < zw * h; o += 64) {
-    const int k = o >> lh, j = o & (h - 1);
-    int s = 0;
-    // DCT-VIII[k][i] = (-1)^k DST-VII[k][n-1-i]: the DST-VII row applied to the reversed input, sign by the parity of k
-    if (trh == 1) { for (int i = 0; i < w; i += 4) s += dot4_resi(*(const uint32_t *) (Mw + k * w + i), rev4_s16(*(const uint2 *) (org + j * w + w - 4 - i)), rev4_s16(*(const uint2 *) (rec + j * w + w - 4 - i))); if (k & 1) s = -s; }
-    else for (int i = 0; i < w; i += 4) s += dot4_resi(*(const uint32_t *) (Mw + k * w + i), *(const uint2 *) (org + j * w + i), *(const uint2 *) (rec + j * w + i));
-    tmp[o] = (s + rnd1) >> shift1;
-  }
-  wave_sync();
-  const int need_sqrt = (lw + lh) & 1;
-  const int qscale = L.t.qscale[need_sqrt * 6 + qp % 6];
-  const int tr_shift = 15 - bd - ((lw + lh) >> 1) + (need_sqrt ? -1 : 0);
-  const int qbits = 14 + qp / 6 + tr_shift;
-  const long long qadd = (long long) 171 << (qbits - 9);
-  if (given < 0 && (zw < w || zh < h)) { for (int o = lane; o < P; o += 64) lev[o] = 0; wave_sync(); }
-  int abs_sum = 0;
-  if (given < 0) for (int o = lane; o < zw * zh; o += 64) {
-    const int m = o >> lzw, k = o & (zw - 1);
-    int s = 0;
-    if (trv == 1) { for (int j = 0; j < h; j += 4) s += dot4_s32(*(const uint32_t *) (Mh + m * h + j), rev4_s32(*(const I32x4 *) (tmp + k * h + h - 4 - j))); if (m & 1) s = -s; }
-    else for (int j = 0; j < h; j += 4) s += dot4_s32(*(const uint32_t *) (Mh + m * h + j), *(const I32x4 *) (tmp + k * h + j));
-    const int c = (s + rnd2) >> shift2;
-    if (dq) { lev[m * w + k] = (int16_t) c; continue; }
-    const long long t = (long long) iabs(c) * qscale;
-    int q = (int) ((t + qadd) >> qbits);
-    abs_sum += q;
-    if (c < 0) q = -q;
-    q = q < -32768 ? -32768 : q > 32767 ? 32767 : q;
-    lev[m * w + k] = (int16_t) q;
-  }
-  if (given == -2) { wave_sync(); sse_out = 0; cbf_out = 0; return; }      // forward half only (batched full-RD stage)
-  if (dq && given < 0) {
-    wave_sync();
-    abs_sum = wave_depquant<SMALL>(lev, 0, L.par.scratch + (size_t) blockIdx.x * L.par.scratch_per_stream, CI_CUR, w, h, 0, VX_CTX_QtCbf[0], 1, 0, lane);
-  } else abs_sum = given < 0 ? uni(wave_sum_i32(abs_sum)) : given;
-  wave_sync();
-  unsigned long long sse = 0;
-  if (abs_sum > 0) {
-    const int iscale = L.t.iqscale[need_sqrt * 6 + qp % 6];
-    const int right_shift = 6 - (tr_shift + qp / 6);
-    int tbd = 32 + right_shift - 7; if (tbd > 16) tbd = 16;
-    const int in_min = -(1 << (tbd - 1)), in_max = (1 << (tbd - 1)) - 1;
-    int16_t *deq = (int16_t *) tmp, *tcol = deq + zw * zh;       // as in wave_code_block: coefficients dequantised once, 16-bit intermediate
-    if (dq) wave_dequant_dq(lev, deq, w, h, zw, zh, bd, qp, lane);
-    else {
-    for (int o = lane; o < zw * zh; o += 64) {
-      const int m = o >> lzw, k = o & (zw - 1);
-      int q = lev[m * w + k]; q = q < in_min ? in_min : q > in_max ? in_max : q;
-      int v = right_shift > 0 ? (q * iscale + (1 << (right_shift - 1))) >> right_shift : (q * iscale) << (-right_shift);
-      deq[o] = (int16_t) (v < -32768 ? -32768 : v > 32767 ? 32767 : v);
-    }
-    wave_sync();
-    }
-    for (int o = lane; o < zw * h; o += 64) {
-      const int j = o >> lh, i = o & (h - 1);
-      int s = 0;
-      if (trv == 1) for (int k = 0; k < zh; k++) { const int v = Mh[k * h + h - 1 - i] * deq[(k << lzw) + j]; s += (k & 1) ? -v : v; }
-      else for (int k = 0; k < zh; k++) s += Mh[k * h + i] * deq[(k << lzw) + j];
-      int v = (s + 64) >> 7;
-      tcol[o] = (int16_t) (v < -32768 ? -32768 : v > 32767 ? 32767 : v);
-    }
-    wave_sync();
-    const int ishift2 = (6 + 15 - 1) - bd, irnd2 = 1 << (ishift2 - 1);
-    const int mx = (1 << bd) - 1;
-    for (int o = lane; o < P; o += 64) {
-      const int j2 = o >> lw, i2 = o & (w - 1);
-      int s = 0;
-      if (trh == 1) for (int k = 0; k < zw; k++) { const int v = Mw[k * w + w - 1 - i2] * tcol[k * h + j2]; s += (k & 1) ? -v : v; }
-      else for (int k = 0; k < zw; k++) s += Mw[k * w + i2] * tcol[k * h + j2];
-      int r = (s + irnd2) >> ishift2;
-      r = r < -32768 ? -32768 : r > 32767 ? 32767 : r;
-      int v = rec[o] + (int) (int16_t) r;
-      v = v < 0 ? 0 : v > mx ? mx : v;
-      rec[o] = (int16_t) v;
-      const int d = org[o] - v;
-      sse += (unsigned long long) (d * d);
-    }
-  } else {
-    for (int o = lane; o < P; o += 64) { const int d = org[o] - rec[o]; sse += (unsigned long long) (d * d); }
-  }
-  wave_sync();
-  sse_out = wave_sum_u64(sse);
-  cbf_out = abs_sum > 0;
-}
-// The block pipeline of one sub-partition of an ISP CU (TU of tw x th samples; 1 x N, 2 x N, N x 1, N x 2 and larger): implicit transform selection (TrQuant::getTrTypes
-// 752-780: DST-VII along a side of 4..16 samples, DCT-II otherwise), the one-stage forms of N x 1 / 1 x N blocks (xT 895-914, xIT 970-983), dependent quantisation
-// against the context set ci (the estimator's live contexts: the sub-partitions of a CU are coded one after the other) with the cbf context cbf_ctx (< 0: the cbf is
-// inferred), dequantisation, inverse, reconstruction over the prediction in rec, SSE.  org / rec / lev: tiles of the CU (stride cst) at the TU's origin.
-// given >= 0: the levels in lev are taken as coded (cbf = given): decoder half only.  tmp: th * min(32, tw) int32 (and its int16 re-use).
-// LDSP: every tile of the call lives in LDS (the search of ISP CUs of at most 128 samples)
-template <bool LDSP>
-__device__ __noinline__ void wave_code_block_isp(const int16_t *org, int16_t *rec, int16_t *lev, int cst, int32_t *tmp, int16_t *cf, uint8_t *scratch, int w, int h, int bd, int qp,
-                                                 int lane, unsigned long long &sse_out, int &cbf_out, int given, int ci, int cbf_ctx)
-{
-  org = uni_p(org); rec = uni_p(rec); lev = uni_p(lev); tmp = uni_p(tmp); cf = uni_p(cf); scratch = uni_p(scratch); ci = uni(ci); cbf_ctx = uni(cbf_ctx);
-  if (LDSP) { org = as_lds(org); rec = as_lds(rec); lev = as_lds(lev); tmp = as_lds(tmp); cf = as_lds(cf); }
-  // cf: a dense w * h int16 tile for the coefficients / levels (the trellis and the residual syntax take stride w)
-  w = uni(w); h = uni(h); bd = uni(bd); qp = uni(qp); given = uni(given); cst = uni(cst);
-  const int trh = (w >= 4 && w <= 16) ? 2 : 0, trv = (h >= 4 && h <= 16) ? 2 : 0;
-  const int P = w * h, lw = ilog2i(w), lh = ilog2i(h);
-  const int zw = imin(w, 32), zh = imin(h, 32), lzw = ilog2i(zw);
-  const int8_t *Mw = w > 1 ? tr_matrix<false>(trh, w) : nullptr, *Mh = h > 1 ? tr_matrix<false>(trv, h) : nullptr;
-  const int oneD = w == 1 || h == 1;
-  ISP_T(i0);
-  if (given < 0) {
-    if (!oneD) {
-      const int shift1 = lw + bd + 6 - 15, shift2 = lh + 6;
-      const int rnd1 = shift1 > 0 ? 1 << (shift1 - 1) : 0, rnd2 = 1 << (shift2 - 1);
-      for (int o = lane; o < zw * h; o += 64) {
-        const int k = o >> lh, j = o & (h - 1);
-        int s = 0;
-        for (int i = 0; i < w; i++) s += Mw[k * w + i] * (org[j * cst + i] - rec[j * cst + i]);
-        tmp[o] = (s + rnd1) >> shift1;
-      }
-      wave_sync();
-      for (int o = lane; o < P; o += 64) cf[o] = 0;
-      wave_sync();
-      for (int o = lane; o < zw * zh; o += 64) {
-        const int m = o >> lzw, k = o & (zw - 1);
-        int s = 0;
-        for (int j = 0; j < h; j++) s += Mh[m * h + j] * tmp[k * h + j];
-        cf[m * w + k] = (int16_t) ((s + rnd2) >> shift2);
-      }
-    } else {
-      const int n = w * h, ln = lw + lh, zn = imin(n, 32), shift = ln + bd + 6 - 15, rnd = shift > 0 ? 1 << (shift - 1) : 0, step = w == 1 ? cst : 1;
-      const int8_t *M = w == 1 ? Mh : Mw;
-      for (int o = lane; o < n; o += 64) {
-        int s = 0;
-        if (o < zn) for (int i = 0; i < n; i++) s += M[o * n + i] * (org[i * step] - rec[i * step]);
-        cf[o] = (int16_t) (o < zn ? (s + rnd) >> shift : 0);
-      }
-    }
-    wave_sync();
-  } else {
-    for (int o = lane; o < P; o += 64) cf[o] = lev[(o >> lw) * cst + (o & (w - 1))];
-    wave_sync();
-  }
-  int abs_sum = given;
-  ISP_T(i1);
-  if (given < 0) abs_sum = LDSP ? wave_depquant<true>(nullptr, (int) (cf - (L.wm[uni(VTX >> 6)].slot + BUF)), scratch, ci, w, h, 0, cbf_ctx, 0, 0, lane)
-                                : wave_depquant<false>(cf, 0, scratch, ci, w, h, 0, cbf_ctx, 0, 0, lane);
-  wave_sync();
-  ISP_T(i2);
-  if (given < 0) { for (int o = lane; o < P; o += 64) lev[(o >> lw) * cst + (o & (w - 1))] = cf[o]; }
-  unsigned long long sse = 0;
-  const int mx = (1 << bd) - 1;
-  if (abs_sum > 0) {
-    int16_t *deq = (int16_t *) tmp, *tcol = deq + zw * zh;
-    wave_dequant_dq(cf, deq, w, h, zw, zh, bd, qp, lane);
-    const int ishift2 = (6 + 15 - 1) - bd;
-    if (!oneD) {
-      for (int o = lane; o < zw * h; o += 64) {
-        const int j = o >> lh, i = o & (h - 1);
-        int s = 0;
-        for (int k = 0; k < zh; k++) s += Mh[k * h + i] * deq[(k << lzw) + j];
-        const int v = (s + 64) >> 7;
-        tcol[o] = (int16_t) (v < -32768 ? -32768 : v > 32767 ? 32767 : v);
-      }
-      wave_sync();
-      const int irnd2 = 1 << (ishift2 - 1);
-      for (int o = lane; o < P; o += 64) {
-        const int j2 = o >> lw, i2 = o & (w - 1);
-        int s = 0;
-        for (int k = 0; k < zw; k++) s += Mw[k * w + i2] * tcol[k * h + j2];
-        int r = (s + irnd2) >> ishift2;
-        r = r < -32768 ? -32768 : r > 32767 ? 32767 : r;
-        int v = rec[j2 * cst + i2] + (int) (int16_t) r;
-        v = v < 0 ? 0 : v > mx ? mx : v;
-        rec[j2 * cst + i2] = (int16_t) v;
-        const int d = org[j2 * cst + i2] - v;
-        sse += (unsigned long long) (d * d);
-      }
-    } else {
-      const int n = w * h, zn = imin(n, 32), sh = ishift2 + 1, rnd = 1 << (sh - 1), step = w == 1 ? cst : 1;
-      const int8_t *M = w == 1 ? Mh : Mw;
-      for (int o = lane; o < n; o += 64) {
-        int s = 0;
-        for (int k = 0; k < zn; k++) s += M[k * n + o] * deq[k];
-        int r = (s + rnd) >> sh;
-        r = r < -32768 ? -32768 : r > 32767 ? 32767 : r;
-        int v = rec[o * step] + (int) (int16_t) r;
-        v = v < 0 ? 0 : v > mx ? mx : v;
-        rec[o * step] = (int16_t) v;
-        const int d = org[o * step] - v;
-        sse += (unsigned long long) (d * d);
-      }
-    }
-  } else {
-    for (int o = lane; o < P; o += 64) { const int a = (o >> lw) * cst + (o & (w - 1)); const int d = org[a] - rec[a]; sse += (unsigned long long) (d * d); }
-  }
-  wave_sync();
-  sse_out = wave_sum_u64(sse);
-  cbf_out = abs_sum > 0;
-  { ISP_T(i3); ISP_ADD(16, i0, i1); ISP_ADD(17, i1, i2); ISP_ADD(18, i2, i3); }
-}
+// ------------------------------------------------------------------------------------------------ transform + quant (one wave)
+#include "vvcx_trquant_dev.h"
 // CABACWriter::mts_coding 3885-3941 for a TU where MTS is allowed and transform skip is not (JVET_O0294 contexts); lane 0 / thread 0
 template <bool WR = false>
 __device__ inline void enc_mts_idx(Cab &cb, int mts)
@@ -2205,9 +1728,6 @@ __device__ inline void enc_lfnst_idx(Cab &cb, int ch, int w, int h, int mip, int
 // read from the TS context sets, Quant::dequant (CL/Quant.cpp:423-549) without the sqrt(2) adjustment at max(QP', 4) inverts it, and residual_codingTS
 // (EL/CABACWriter.cpp:4306-4555) codes the levels in forward scan order with a budget of 2 * w * h context-coded bins.  BDPCM is off (BIN/encoder_intra.cfg).
 __device__ inline int ts_allowed(const VxParams &p, int w, int h) { return (p.tools & TOOL_TS) && w <= 32 && h <= 32; }      // TU::isTSAllowed (CL/UnitTools.cpp:4524-4546), TransformSkipLog2MaxSize 5
-__device__ inline int ts_shift(int w, int h, int bd) { return 15 - bd - ((ilog2i(w) + ilog2i(h)) >> 1); }                     // getTransformShift, TU::needsSqrt2Scale false for TS
-__device__ inline int ts_scale(int r, int sh) { return sh >= 0 ? r * (1 << sh) : (r + (1 << (-sh - 1))) >> -sh; }
-__device__ inline int ts_qp(int qp) { return imax(qp, 4); }                                                                   // QpParam::Qp(isTransformSkip), min_qp_prime_ts_minus4 0
 // CABACWriter::mts_coding 3885-3941 of a luma TU with cbf (not an ISP one): transform_skip_flag where TU::isTSAllowed, then the MTS index where TU::isMTSAllowed
 template <bool WR = false>
 __device__ inline void enc_tu_mts(Cab &cb, int w, int h, int mts)
@@ -2381,42 +1901,6 @@ __device__ __noinline__ void rc_ts_serial(Cab &cb, const int16_t *lv, int w, int
     }
   }
 #undef TS_BIN
-}
-// sum |xTransformSkip(org - pred)| scaled as TrQuant::transformNxN (1049-1124) scales the transform-skip entry of its pruning; optionally the coefficients to coef_out
-__device__ inline int wave_ts_fwd(const int16_t *org, const int16_t *pred, int16_t *coef_out, int w, int h, int bd, int lane)
-{
-  const int P = w * h, sh = ts_shift(w, h, bd);
-  int sa = 0;
-  for (int e = lane; e < P; e += 64) { const int c = ts_scale(org[e] - pred[e], sh); if (coef_out) coef_out[e] = (int16_t) c; sa += iabs(c); }
-  sa = wave_sum_i32(sa);
-  const double scale = ((ilog2i(w) + ilog2i(h)) & 1) ? 1.0 / 1.414213562 : 1.0;
-  return (int) ((double) sa * scale);
-}
-// decoder half of a transform-skip block by one wave: Quant::dequant, xITransformSkip, reconstruction over the prediction in rec, SSE against org.
-// raw: rec receives the bare residual (leaf test).  cbf 0: the prediction is the reconstruction.
-__device__ __noinline__ void wave_ts_recon(const int16_t *org, int16_t *rec, const int16_t *lev, int w, int h, int bd, int qp, int cbf, int lane, unsigned long long &sse_out, int raw = 0)
-{
-  org = uni_p(org); rec = uni_p(rec); lev = uni_p(lev); raw = uni(raw);
-  w = uni(w); h = uni(h); bd = uni(bd); qp = uni(qp); cbf = uni(cbf);
-  const int P = w * h, q = ts_qp(qp), sh = ts_shift(w, h, bd), scale = L.t.iqscale[q % 6], right_shift = 6 - (sh + q / 6), mx = (1 << bd) - 1;
-  int tbd = 32 + right_shift - 7; if (tbd > 16) tbd = 16;
-  const int in_min = -(1 << (tbd - 1)), in_max = (1 << (tbd - 1)) - 1;
-  unsigned long long sse = 0;
-  for (int e = lane; e < P; e += 64) {
-    int r = 0;
-    if (cbf) {
-      int l = lev[e]; l = l < in_min ? in_min : l > in_max ? in_max : l;
-      int v = right_shift > 0 ? (l * scale + (1 << (right_shift - 1))) >> right_shift : (l * scale) * (1 << -right_shift);
-      v = v < -32768 ? -32768 : v > 32767 ? 32767 : v;
-      r = (int) (int16_t) (sh >= 0 ? (v + (sh == 0 ? 0 : 1 << (sh - 1))) >> sh : v * (1 << -sh));
-    }
-    if (raw) { rec[e] = (int16_t) r; continue; }
-    int v = rec[e] + r; v = v < 0 ? 0 : v > mx ? mx : v;
-    rec[e] = (int16_t) v;
-    const int d = org[e] - v; sse += (unsigned long long) (d * d);
-  }
-  wave_sync();
-  sse_out = wave_sum_u64(sse);
 }
 
 // ------------------------------------------------------------------------------------------------ parallel operations
