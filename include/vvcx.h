@@ -307,7 +307,8 @@ int  vvcx_resident_streams(const vvcx_handle *h);
 int  vvcx_distortion_batch(const int16_t *a, const int16_t *b, int w, int h, int n, uint64_t *out, int device);
 /* intra prediction of n blocks of one picture: reco = planar 4:2:0 samples of the handle's size and bit depth (uint8 / uint16),
  * coded[2] = one byte per 4x4 luma unit (uw x uh, 1 = already reconstructed) for the luma and the chroma tree.
- * x, y, w, h in samples of the component; mode 0..66, mrl 0/1/3 (luma).  pred: concatenated w*h tiles */
+ * x, y, w, h in samples of the component; mode 0..66, mrl 0/1/3 (luma); for comp 1 / 2 also mode 67 / 68 / 69 (LM, MDLM_L, MDLM_T: the co-located luma of reco[0]
+ * down-sampled, line parameters from the neighbours the chroma-tree map allows; blocks 4x2 .. 32x32 at even x, y).  pred: concatenated w*h tiles */
 typedef struct { int32_t comp, x, y, w, h, mode, mrl; } vvcx_pred_case;
 int  vvcx_intra_pred_batch(vvcx_handle *h, const void *const reco[3], const uint8_t *const coded[2], const vvcx_pred_case *cases, int n, int16_t *pred);
 /* CtxStore initialisation of an I slice (CL/Contexts.cpp:135-151) and the estimator's model update over a bin string */

@@ -1454,12 +1454,15 @@ extern "C" int vvcx_intra_pred_batch(vvcx_handle *h, const void *const reco[3], 
   if (n == 0) return VVCX_OK;
   ON_DEVICE(h->cfg.device);
   const int bps = h->cfg.bit_depth == 8 ? 1 : 2, W = h->cfg.pic_w, H = h->cfg.pic_h;
-  std::vector<int> off((size_t) n); size_t total = 0;
+  std::vector<int> off((size_t) n); size_t total = 0; bool any_lm = false;
   for (int i = 0; i < n; i++) {
     const vvcx_pred_case &c = cases[i];
     const int cw = c.comp ? W >> 1 : W, chh = c.comp ? H >> 1 : H;
-    if (c.comp < 0 || c.comp > 2 || !pow2_block(c.w, c.h) || c.x < 0 || c.y < 0 || c.x + c.w > cw || c.y + c.h > chh || c.mode < 0 || c.mode > 66 ||
+    const bool lm = c.mode >= 67 && c.mode <= 69;                          // LM / MDLM_L / MDLM_T: chroma blocks of at least 4 x 2 samples, at most 32 x 32 (a 64 x 64 chroma-tree node)
+    if (c.comp < 0 || c.comp > 2 || !pow2_block(c.w, c.h) || c.x < 0 || c.y < 0 || c.x + c.w > cw || c.y + c.h > chh || c.mode < 0 || (c.mode > 66 && !lm) ||
+        (lm && (c.comp == 0 || c.w < 4 || c.w > 32 || c.h > 32 || (c.x & 1) || (c.y & 1))) ||
         (c.mrl != 0 && (c.comp != 0 || (c.mrl != 1 && c.mrl != 3)))) return fail(VVCX_ERR_ARG, "bad prediction case %d", i);
+    any_lm |= lm;
     off[(size_t) i] = (int) total; total += (size_t) c.w * c.h;
   }
   DevBuf<uint8_t> dplane[3]; DevBuf<VxUnit> dunits; DevBuf<VxFrameDev> dframe; DevBuf<VxLeafPred> dcases; DevBuf<int> doff; DevBuf<int16_t> dpred;
@@ -1481,6 +1484,8 @@ extern "C" int vvcx_intra_pred_batch(vvcx_handle *h, const void *const reco[3], 
   HIPCHK(dpred.alloc(total));
   VxParams p; memset(&p, 0, sizeof p);
   p.pic_w = W; p.pic_h = H; p.bit_depth = h->cfg.bit_depth; p.tools = h->cfg.tools; p.uw = h->uw; p.uh = h->uh; p.frames = dframe.p;
+  DevBuf<uint8_t> dscr;                                                    // the CCLM modes keep the down-sampled luma of a big block in the workgroup's scratch slice (VXD_OFF_LM)
+  if (any_lm) { HIPCHK(dscr.alloc((size_t) n * VXD_OFF_DQ)); p.scratch = dscr.p; p.scratch_per_stream = VXD_OFF_DQ; }
   if (bps == 1) hipLaunchKernelGGL(vvcx_leaf_pred_kernel_u8, dim3((unsigned) n), dim3(VXD_NT), 0, 0, p, dcases.p, dpred.p, doff.p);
   else hipLaunchKernelGGL(vvcx_leaf_pred_kernel_u16, dim3((unsigned) n), dim3(VXD_NT), 0, 0, p, dcases.p, dpred.p, doff.p);
   HIPCHK(hipGetLastError());

@@ -1529,6 +1529,9 @@ template <int BW> __device__ inline void row_diff(const int16_t *o, const int16_
     for (int k = 0; k < BW; k += 8) { const vs8 a = *(const vs8 *) (o + k), b = *(const vs8 *) (q + k); for (int i = 0; i < 8; i++) v[k + i] = a[i] - b[i]; }
   } else { for (int i = 0; i < BW; i++) v[i] = o[i] - q[i]; }
 }
+// The int16 scratch holds the row pass of the Hadamard tile: |v| <= BW * (2^bit_depth - 1), which is 16 * 1023 = 16368 for the widest tile at 10 bit, the deepest the
+// library takes (vvcx_create).  One more bit of depth at BW == 16 would still fit (16 * 2047 = 32752); 12 bit would not.
+static_assert(16 * ((1 << 10) - 1) <= INT16_MAX, "row pass of a 16-wide Hadamard tile must fit the int16 scratch");
 template <int BW> __device__ inline void row_store(int16_t *d, const int *v)
 {
   if constexpr (BW == 4) { vs4 a; for (int i = 0; i < 4; i++) a[i] = (short) v[i]; *(vs4 *) d = a; }
@@ -4724,6 +4727,14 @@ __device__ void leaf_pred(const VxParams &p, const VxLeafPred *cases, int16_t *o
   if (VTX == 0) { L.cur_tile = 0; L.nx = c.x; L.ny = c.y; L.nw = c.w; L.nh = c.h; }
   __syncthreads();
   const int luma = c.comp == 0;
+  int16_t *o = out + out_off[blockIdx.x];
+  if (c.mode >= LM_CHROMA) {                // LM / MDLM_L / MDLM_T of a chroma block, as op_chroma_rd sets them up: the references of both components, the down-sampled luma and
+    uint8_t *scratch = p.scratch + (size_t) blockIdx.x * p.scratch_per_stream;      // the line parameters (blocks of more than BUF / 2 samples keep the luma in the workgroup's scratch slice)
+    for (int k = 1; k <= 2; k++) build_refs<T>(p, fd, k, c.x, c.y, c.w, c.h, 0, 1);
+    cclm_prepare<T>(p, fd, scratch, c.x, c.y, c.w, c.h);
+    if ((VTX >> 6) == 0) chroma_pred_wave(o, lm_in_buf(scratch, 2 * c.w * c.h), c.comp - 1, c.mode, c.w, c.h, p.bit_depth, VTX & 63);
+    return;
+  }
   build_refs<T>(p, fd, c.comp, c.x, c.y, c.w, c.h, 0, luma ? 3 : 1);
   __syncthreads();
   if (VTX < 4) {
@@ -4734,7 +4745,6 @@ __device__ void leaf_pred(const VxParams &p, const VxLeafPred *cases, int16_t *o
   Ipa ip; init_pred_params(c.w, c.h, luma, c.mode, c.mrl, ip);
   const int set = luma ? luma_set(c.mrl, ip.ref_filter) : c.comp - 1;
   const int dcv = L.dc_val[luma ? luma_set(c.mrl, 0) : c.comp - 1];
-  int16_t *o = out + out_off[blockIdx.x];
   for (int i = VTX; i < c.w * c.h; i += NT) { const int py = i >> ilog2i(c.w), px = i & (c.w - 1); o[i] = (int16_t) pred_sample(L.refs[set][0], L.refs[set][1], c.w, c.h, px, py, ip, c.mode, luma, p.bit_depth, dcv); }
 }
 extern "C" __global__ void __launch_bounds__(NT, VXD_WPE) vvcx_leaf_pred_kernel_u8(VxParams p, const VxLeafPred *cases, int16_t *out, const int *out_off) { leaf_pred<uint8_t>(p, cases, out, out_off); }

@@ -370,7 +370,7 @@ class VvcxEncoder:
 
     def intra_pred_batch(self, reco, coded, cases):
         """reco: 3 host planes (uint8 / uint16) of the picture; coded: 2 uint8 maps [uh, uw] (luma tree, chroma tree);
-        cases: structured array PRED_CASE_DTYPE -> list of int16 [h, w] predictions"""
+        cases: structured array PRED_CASE_DTYPE (mode 0..66; 67..69 = LM / MDLM_L / MDLM_T for comp 1, 2) -> list of int16 [h, w] predictions"""
         reco = [np.ascontiguousarray(p) for p in reco]
         coded = [np.ascontiguousarray(c, np.uint8) for c in coded]
         cases = np.ascontiguousarray(cases, PRED_CASE_DTYPE)

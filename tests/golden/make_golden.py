@@ -1210,8 +1210,344 @@ def gen_decision_helpers2():
     print("decision helper rows", len(a), "can use ISP", int(a[a[:, 2] == 0][:, 3].sum()), "TS allowed", int(a[:, 9].sum()), "MTS allowed", int(a[:, 10].sum()), "dual tree", set(a[:, 11].tolist()), "LM list", a[0, 14:18].tolist())
 
 
+# ---- leaf fixtures at every block shape and at the range edges (intra_shapes_8 / intra_shapes_10 / cclm_shapes / mip_range / dist_range): seeds of their own, the shared rng
+# stream is not touched.  Pictures and coded maps are not stored: tests/oracle_lib.py leaf_picture / leaf_coded_map regenerate them for the generator and for the tests alike.
+def _olib():
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_lib as O
+    return O
+
+
+def _report(name, ncases):
+    print("%s: %d bytes, %d cases" % (name, os.path.getsize(os.path.join(HERE, name)), ncases))
+    assert os.path.getsize(os.path.join(HERE, name)) <= 1043003, name        # no new fixture above the largest one there was (lfnst.npz)
+
+
+LEAF_LUMA_SHAPES = [(w, h) for w in (4, 8, 16, 32, 64) for h in (4, 8, 16, 32, 64)]
+LEAF_CHROMA_SHAPES = [(w, h) for w in (8, 16, 32, 64) for h in (4, 8, 16, 32, 64) if w * h >= 64]       # luma units, gen_intra's rule: chroma blocks 4x2 .. 32x32
+
+
+def leaf_positions(w, h):
+    """block positions (luma samples) every shape takes: interior at y % 128 == 64, x == 0, y == 0, the picture's corner (no neighbour at all), the first row of the second CTU
+    row, the right picture edge (above-right outside the picture), the bottom picture edge (below-left outside)"""
+    return ((64, 64), (0, 72), (72, 0), (0, 0), (40, 128), (192 - w, 32), (80, 192 - h))
+
+
+def leaf_modes(samples):
+    """all 67 modes for blocks of at most 256 samples; the others take planar, DC, the four corner / axis directions and every third angular mode from 2, which
+    includes the wide-angle substitutions at both ends for every aspect ratio (2, 5, 8, 11, 14 and 53, 56, 59, 62, 65)"""
+    return list(range(67)) if samples <= 256 else sorted({0, 1, 18, 34, 50, 66} | set(range(2, 66, 3)))
+
+
+class _LeafEnv:
+    """the reference's coding structure of one 192 x 192 picture: loads a pattern's planes once, predicts a block with the neighbourhood of a coded map"""
+    def __init__(self, bd):
+        self.O = _olib(); self.bd = bd; self.env = R.ref_env_create(192, 192, bd); self.pattern = None
+
+    def pred(self, pattern, kind, comp, x, y, w, h, mode, mrl, check=True):
+        if pattern != self.pattern:
+            for c, pl in enumerate(self.O.leaf_picture(self.bd, pattern)):
+                R.ref_env_set_reco(self.env, c, P(pl), pl.shape[1])
+            self.pattern = pattern
+        ch = 1 if comp else 0
+        R.ref_env_reset(self.env)
+        for by, bx in zip(*np.nonzero(self.O.leaf_coded_map(x, y, w, h, kind))):
+            R.ref_env_add_cu(self.env, ch, int(bx) * 8, int(by) * 8, 8, 8, 0, 3, 1)
+        out = np.zeros((w >> ch) * (h >> ch), np.int16); mpm = np.zeros(6, np.uint32)
+        rc = R.ref_env_pred(self.env, comp, x, y, w, h, mode, mrl, 0, P(out), P(mpm))
+        assert rc == 0 or not check, (comp, x, y, w, h, mode, mrl)
+        return out if rc == 0 else None
+
+
+def leaf_intra_class(ch, w, h, mode, mrl):
+    """which arithmetic of IntraPrediction::predIntraAng a case runs (block size of the component): planar, dc, hv (pure horizontal / vertical, PDPC), cubic / smooth (fractional
+    angle through the cubic or the smoothing interpolation filter), int (whole-sample angle), chroma (two-tap interpolation); and whether getWideAngle remapped the mode"""
+    l2 = lambda v: int(v).bit_length() - 1
+    pm, wide = mode, ""
+    if 1 < mode < 67:
+        ms = (0, 6, 10, 12, 14, 15)[abs(l2(w) - l2(h))]
+        if w > h and mode < 2 + ms:
+            pm, wide = mode + 65, "wide"
+        elif h > w and mode > 66 - ms:
+            pm, wide = mode - 65, "tall"
+    if mode < 2:
+        return ("planar", "dc")[mode], wide
+    if pm in (18, 50):
+        return "hv", wide
+    ang = (0, 1, 2, 3, 4, 6, 8, 10, 12, 14, 16, 18, 20, 23, 26, 29, 32, 35, 39, 45, 51, 57, 64, 73, 86, 102, 128, 171, 256, 341, 512, 1024)[abs(pm - 50 if pm >= 34 else pm - 18)]
+    if ang % 32 == 0:
+        return "int", wide
+    if ch:
+        return "chroma", wide
+    smooth = mrl == 0 and min(abs(pm - 18), abs(pm - 50)) > (24, 24, 24, 14, 2, 0, 0, 0)[(l2(w) + l2(h)) >> 1]
+    return ("smooth" if smooth else "cubic"), wide
+
+
+def gen_intra_shapes():
+    """vvcx_intra_pred_batch's whole path (reference samples, reference filter, angular / planar / DC prediction, PDPC) through the reference's initIntraPatternChType +
+    predIntraAng at every luma shape 4..64 x 4..64 and every chroma shape 4x2 .. 32x32 (both components), at the seven positions of leaf_positions, on the three full-range
+    pictures of leaf_picture and the four neighbourhood rules of leaf_coded_map, with MRL 0, 1 and 3 wherever the reference allows them.  Position, picture and neighbourhood
+    rotate over the modes of a shape (no cross product); one file per bit depth."""
+    for bd in (8, 10):
+        E = _LeafEnv(bd); mx = (1 << bd) - 1
+        meta, preds = [], []
+        for ch, shapes in ((0, LEAF_LUMA_SHAPES), (1, LEAF_CHROMA_SHAPES)):
+            for si, (w, h) in enumerate(shapes):
+                pos = leaf_positions(w, h)
+                for comp in ((0,) if ch == 0 else (1, 2)):
+                    for mi, mode in enumerate(leaf_modes((w >> ch) * (h >> ch))):
+                        p, r = (mi + si + comp) % 7, mi // 7
+                        x, y = pos[p]
+                        pattern, kind = (r + p + si) % 3, (r + 2 * p + si + comp) % 4
+                        for mrl in ((0, 1, 3) if (ch == 0 and mode != 0 and y % 128 != 0) else (0,)):      # MRL wherever the reference allows it: not planar, not the first row of a CTU
+                            meta.append((pattern, kind, comp, x, y, w, h, mode, mrl))
+        for m in sorted(meta):                                           # by picture, then by neighbourhood: one reference picture load per pattern
+            preds.append((m, E.pred(*m)))
+        preds = dict(preds)
+        meta = np.array(meta, np.int16)
+        # coverage, so that the fixture cannot quietly lose its point
+        seen = {}
+        for m in map(tuple, meta.tolist()):
+            pattern, kind, comp, x, y, w, h, mode, mrl = m
+            ch = 1 if comp else 0
+            for key in (("pattern", comp, w, h, pattern), ("kind", comp, w, h, kind), ("pos", comp, w, h, leaf_positions(w, h).index((x, y)))):
+                seen[key] = 1
+            if mrl and y % 128 == 64:
+                seen[("mrl64", w, h, mrl)] = 1
+            if pattern == 0:
+                cls, wide = leaf_intra_class(ch, w >> ch, h >> ch, mode, mrl)
+                for k in ((cls,) if ch == 0 else ()) + ((wide,) if wide and ch == 0 else ()):
+                    seen[("lo", k)] = seen.get(("lo", k), 0) + int((preds[m] == 0).any()); seen[("hi", k)] = seen.get(("hi", k), 0) + int((preds[m] == mx).any())
+                    seen[("both", k)] = seen.get(("both", k), 0) + int((preds[m] == 0).any() and (preds[m] == mx).any())
+        for comp, shapes in ((0, LEAF_LUMA_SHAPES), (1, LEAF_CHROMA_SHAPES), (2, LEAF_CHROMA_SHAPES)):
+            for (w, h) in shapes:
+                assert all(("pattern", comp, w, h, k) in seen for k in range(3)) and all(("kind", comp, w, h, k) in seen for k in range(4)), (comp, w, h)
+                assert all(("pos", comp, w, h, k) in seen for k in range(7)), (comp, w, h)
+                assert comp or (("mrl64", w, h, 1) in seen and ("mrl64", w, h, 3) in seen), (w, h)
+        # predictions from the alternating picture reach 0 and 2^bd - 1 in every class.  Planar cannot do both inside one block (its bottom-left and top-right samples weigh in
+        # every output sample) and DC is one value plus PDPC, so for those two the two ends come from different cases; every other class has a case that holds both
+        for k in ("planar", "dc", "hv", "cubic", "smooth", "wide", "tall"):
+            assert seen[("lo", k)] > 0 and seen[("hi", k)] > 0, (bd, k, seen[("lo", k)], seen[("hi", k)])
+            assert k in ("planar", "dc") or seen[("both", k)] > 0, (bd, k)
+        print("intra_shapes %d bit: cases with 0 | max | both by class" % bd, {k: (seen[("lo", k)], seen[("hi", k)], seen[("both", k)]) for k in ("planar", "dc", "hv", "cubic", "smooth", "wide", "tall")})
+        name = "intra_shapes_%d.npz" % bd
+        np.savez_compressed(os.path.join(HERE, name), meta=meta, pred=np.concatenate([preds[tuple(m)] for m in meta.tolist()]).astype(np.uint8 if bd == 8 else np.uint16))
+        _report(name, len(meta))
+
+
+def range_line(kind, n, mx, g):
+    """reference lines of the MIP range fixture: 0 all 0, 1 all max, 2 / 3 alternating 0 / max in both phases, 4..6 one step 0 -> max at a quarter, the middle, three quarters,
+    7 one step max -> 0 in the middle, 8 uniform full-range noise"""
+    i = np.arange(n)
+    if kind < 2:
+        v = np.full(n, kind * mx)
+    elif kind < 4:
+        v = ((i + kind) & 1) * mx
+    elif kind < 7:
+        v = (i >= n * (kind - 3) // 4) * mx
+    elif kind == 7:
+        v = (i < n // 2) * mx
+    else:
+        v = g.integers(0, mx + 1, n)
+    return np.asarray(v).astype(np.int16)
+
+
+def gen_mip_range():
+    """gen_mip's loop (every shape MIP allows, every mode, 8 and 10 bit) on saturated, alternating, stepped and full-range reference lines: the boundary down-sampling sums and
+    the clip after the matrix product at both ends of the range.  The line kinds rotate over the modes and shapes, top and left independently."""
+    R.ref_mip_pred.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    g = np.random.default_rng(926)
+    meta, refs, preds = [], [], []
+    for bd in (8, 10):
+        mx, si, lo, hi = (1 << bd) - 1, 0, 0, 0
+        for w in (4, 8, 16, 32, 64):
+            for h in (4, 8, 16, 32, 64):
+                if w > 4 * h or h > 4 * w:
+                    continue
+                nm = 35 if (w == 4 and h == 4) else 19 if (w <= 8 and h <= 8) else 11
+                for mode in range(nm):
+                    kt, kl = (mode + si) % 9, (4 * mode + 2 * si + 1) % 9
+                    top, left = range_line(kt, w, mx, g), range_line(kl, h, mx, g)
+                    out = np.zeros(w * h, np.int16)
+                    assert R.ref_mip_pred(w, h, bd, mode, P(top), P(left), P(out)) == 0
+                    meta.append((bd, w, h, mode, kt, kl)); refs.append(np.concatenate([top, left])); preds.append(out)
+                    if kt > 1 or kl > 1:                             # the clip, not a flat block: lines that are not constant
+                        lo += int((out == 0).any()); hi += int((out == mx).any())
+                si += 1
+        assert lo > 20 and hi > 20, (bd, lo, hi)
+        print("mip_range %d bit: cases from non-constant lines that reach 0: %d, max: %d" % (bd, lo, hi))
+    np.savez_compressed(os.path.join(HERE, "mip_range.npz"), meta=np.array(meta, np.int16), refs=np.concatenate(refs), preds=np.concatenate(preds))
+    _report("mip_range.npz", len(meta))
+
+
+def hadamard_sign(k, i):
+    """entry (k, i) of the Hadamard matrix in natural order, as +1 / -1"""
+    return 1 - 2 * (np.vectorize(lambda v: bin(int(v)).count("1"))(np.bitwise_and(k, i)) & 1)
+
+
+def dist_tile(w, h):
+    """the Hadamard tile RdCost::xGetHADs picks for a w x h block (CL/RdCost.cpp:2764-2854)"""
+    if w > h and h % 8 == 0 and w % 16 == 0: return 16, 8
+    if w < h and w % 8 == 0 and h % 16 == 0: return 8, 16
+    if w > h and h % 4 == 0 and w % 8 == 0: return 8, 4
+    if w < h and w % 4 == 0 and h % 8 == 0: return 4, 8
+    if h % 8 == 0 and w % 8 == 0: return 8, 8
+    if h % 4 == 0 and w % 4 == 0: return 4, 4
+    return 2, 2
+
+
+DIST_PATTERNS = ("a max b 0", "a 0 b max", "basis row 1", "basis highest row", "basis product", "checkerboard", "random signs", "one sample", "equal")
+
+
+def gen_dist_range():
+    """SAD / SATD / SSE at the ends of the range: every shape of gen_dist plus the two-sample-wide blocks, 8 and 10 bit.  a - b is +-(2^bd - 1) everywhere in the first seven
+    patterns: one sign (tile * max in the DC coefficient, 16 * 1023 after the row pass of a 16 x 8 tile), signed like a basis function of the tile's Hadamard transform (the same
+    magnitude in another coefficient: horizontal index 1, the highest horizontal index, the highest of both directions), a checkerboard, random signs; then one differing sample, a == b"""
+    g = np.random.default_rng(927)
+    shapes = [(2, h) for h in (2, 4, 8, 16, 32, 64)] + [(w, h) for w in (4, 8, 16, 32, 64) for h in (2, 4, 8, 16, 32, 64)]
+    rows, a_all, b_all = [], [], []
+    for (w, h) in shapes:
+        bw, bh = dist_tile(w, h)
+        yy, xx = np.mgrid[0:h, 0:w]
+        for bd in (8, 10):
+            mx = (1 << bd) - 1
+            for k in range(len(DIST_PATTERNS)):
+                if k < 7:
+                    sgn = (np.ones((h, w), np.int64), -np.ones((h, w), np.int64), hadamard_sign(1, xx % bw), hadamard_sign(bw - 1, xx % bw),
+                           hadamard_sign(bw - 1, xx % bw) * hadamard_sign(bh - 1, yy % bh), 1 - 2 * ((xx + yy) & 1), 1 - 2 * g.integers(0, 2, (h, w)))[k]
+                    a, b = (sgn > 0) * mx, (sgn < 0) * mx
+                else:
+                    a = g.integers(0, mx + 1, (h, w)); b = a.copy()
+                    if k == 7:
+                        j, i = int(g.integers(0, h)), int(g.integers(0, w)); a[j, i], b[j, i] = (mx, 0) if g.integers(0, 2) else (0, mx)
+                a = np.ascontiguousarray(a.astype(np.int16)); b = np.ascontiguousarray(b.astype(np.int16))
+                had = R.ref_hads(P(a), w, P(b), w, w, h, bd); sad = R.ref_sad(P(a), w, P(b), w, w, h, bd); sse = R.ref_sse(P(a), w, P(b), w, w, h, bd)
+                if k < 7:
+                    assert sad == w * h * mx and sse == w * h * mx * mx
+                rows.append((w, h, bd, had, sad, sse, k)); a_all.append(a.ravel()); b_all.append(b.ravel())
+    np.savez_compressed(os.path.join(HERE, "dist_range.npz"), rows=np.array(rows, np.int64), a=np.concatenate(a_all), b=np.concatenate(b_all))
+    _report("dist_range.npz", len(rows))
+
+
+def cclm_oracle(O, planes, coded, bd, comp, x, y, w, h, mode):
+    """the oracle's CCLM trio on a leaf case -> (prediction, a, b, shift, branch set).  The branches are those of xGetLMParameters, found by repeating its choice of the
+    neighbouring sample pairs on the oracle's buffers (checked against the oracle's own a and shift)"""
+    L = O.lib()
+    avail = np.ascontiguousarray(np.repeat(np.repeat(coded, 2, axis=0), 2, axis=1))
+    cx, cy, cw, chh = x // 2, y // 2, w // 2, h // 2
+    Wl = planes[0].shape[1]; plane = planes[comp]
+    ref = np.zeros(4 * 300 * 300, np.int16)
+    L.orc_fill_ref_samples(P(plane), plane.shape[1], plane.shape[1], plane.shape[0], P(avail), avail.shape[1], 1, 1, cx, cy, cw, chh, 0, bd, P(ref))
+    ts = 2 * 64 + 2
+    tmp = np.zeros(ts * ts, np.int16); info = np.zeros(4, np.int32)
+    L.orc_cclm_luma(P(planes[0]), Wl, P(avail), avail.shape[1], 1, Wl // 2, planes[0].shape[0] // 2, cx, cy, cw, chh, int(mode != 67), P(info), P(tmp), ts)
+    a = C.c_int(); b = C.c_int(); sh = C.c_int()
+    L.orc_cclm_params(P(tmp), ts, P(ref), cw, chh, mode, P(info), bd, C.byref(a), C.byref(b), C.byref(sh))
+    pred = np.zeros(cw * chh, np.int16)
+    L.orc_pred_cclm(P(tmp), ts, a.value, b.value, sh.value, bd, cw, chh, P(pred), cw)
+    # the branch taken
+    la, aa, lb, ar = map(int, info)
+    at = al = 0
+    if mode == 69:
+        la = 0; at = 2 * ((cw // 2 if aa else 0) + min(ar, chh // 2))
+    elif mode == 68:
+        aa = 0; al = 2 * ((chh // 2 if la else 0) + min(lb, cw // 2))
+    else:
+        at, al = cw, chh
+    t4, l4 = (0 if la else 1), (0 if aa else 1)
+    pts = []
+    if aa:
+        pts += [(int(tmp[1 + q]), int(ref[1 + q])) for q in [(at >> (2 + t4)) + k * max(1, at >> (1 + t4)) for k in range(min(at, (1 + t4) << 1))]]
+    if la:
+        pts += [(int(tmp[(1 + q) * ts]), int(ref[(1 + q) * (2 * cw + 1)])) for q in [(al >> (2 + l4)) + k * max(1, al >> (1 + l4)) for k in range(min(al, (1 + l4) << 1))]]
+    br = set()
+    if not (la or aa):
+        br.add("none"); assert (a.value, b.value, sh.value) == (0, 1 << (bd - 1), 0)
+    else:
+        if mode != 67:
+            br.add("mdlm extended" if (min(ar, chh // 2) if mode == 69 else min(lb, cw // 2)) > 0 else "mdlm plain")
+        if len(pts) == 2:
+            br.add("two"); pts = [pts[1], pts[0], pts[1], pts[0]]
+        assert len(pts) == 4
+        sl = [q[0] for q in pts]; sc = [q[1] for q in pts]
+        mn, mxg = [0, 2], [1, 3]
+        if sl[mn[0]] > sl[mn[1]]: mn.reverse()
+        if sl[mxg[0]] > sl[mxg[1]]: mxg.reverse()
+        if sl[mn[0]] > sl[mxg[1]]: mn, mxg = mxg, mn
+        if sl[mn[1]] > sl[mxg[0]]: mn[1], mxg[0] = mxg[0], mn[1]
+        diff = ((sl[mxg[0]] + sl[mxg[1]] + 1) >> 1) - ((sl[mn[0]] + sl[mn[1]] + 1) >> 1)
+        diffc = ((sc[mxg[0]] + sc[mxg[1]] + 1) >> 1) - ((sc[mn[0]] + sc[mn[1]] + 1) >> 1)
+        if diff <= 0:
+            br.add("diff0"); assert diff == 0 and a.value == 0 and sh.value == 0
+        else:
+            xl = diff.bit_length() - 1
+            xl += (((diff << 4) >> xl) & 15) != 0
+            if 3 + xl - (abs(diffc).bit_length() if diffc else 0) < 1:
+                assert sh.value == 1 and abs(a.value) in (0, 15)
+                if a.value:
+                    br.add("clamp+" if a.value > 0 else "clamp-")
+            assert sh.value >= 1 and (a.value == 0) == (diffc == 0 or a.value == 0) and (a.value < 0) == (diffc < 0 and a.value != 0)
+            if a.value < 0:
+                br.add("neg")
+            if a.value == 0:
+                br.add("a0")
+    return pred, a.value, b.value, sh.value, br
+
+
+CCLM_BRANCHES = ("diff0", "clamp+", "clamp-", "neg", "a0", "none", "two", "first row", "other row", "mdlm extended", "mdlm plain")
+
+
+def gen_cclm_shapes():
+    """LM / MDLM_L / MDLM_T through the reference (xGetLumaRecPixels + xGetLMParameters + predIntraChromaLM) for every chroma shape of gen_intra_shapes the reference takes,
+    both components, at the positions of leaf_positions (first row of a CTU and not, picture edges, the corner without neighbours), on the four pictures of leaf_picture and the
+    four neighbourhood rules (MDLM with and without its above-right / below-left extension).  Two rounds rotate picture and neighbourhood over (shape, position, component, mode).
+    Every case is classified by the branch of xGetLMParameters it takes, with the oracle once it equals the reference on the case."""
+    O = _olib()
+    meta, preds, hits = [], [], {}
+    for bd in (8, 10):
+        E = _LeafEnv(bd)
+        legal = [(w, h) for (w, h) in LEAF_CHROMA_SHAPES if all(E.pred(2, 3, 1, 64, 64, w, h, mode, 0, check=False) is not None for mode in (67, 68, 69))]
+        print("cclm_shapes %d bit: shapes the reference takes:" % bd, legal)
+        assert (8, 8) in legal and (64, 64) in legal
+        todo = []
+        for rnd in range(2):
+            k = 0
+            for si, (w, h) in enumerate(legal):
+                for p, (x, y) in enumerate(leaf_positions(w, h)):
+                    for comp in (1, 2):
+                        for mode in (67, 68, 69):
+                            todo.append(((k + rnd * 2 + p) % 4, (k // 4 + rnd + si + p) % 4, comp, x, y, w, h, mode)); k += 1
+        todo = sorted(set(todo))
+        for m in todo:
+            pattern, kind, comp, x, y, w, h, mode = m
+            exp = E.pred(pattern, kind, comp, x, y, w, h, mode, 0)
+            got, a, b, sh, br = cclm_oracle(O, O.leaf_picture(bd, pattern), O.leaf_coded_map(x, y, w, h, kind), bd, comp, x, y, w, h, mode)
+            assert np.array_equal(got, exp), ("oracle != reference", bd, m, a, b, sh)
+            for k in br | {"first row" if (y // 2) % 64 == 0 else "other row"}:
+                hits[(bd, comp, k)] = hits.get((bd, comp, k), 0) + 1
+            for k in (("pattern", pattern), ("kind", kind)):
+                hits[(bd, w, h, k)] = 1
+            meta.append((bd,) + m); preds.append(exp)
+        for comp in (1, 2):
+            for k in CCLM_BRANCHES:
+                assert hits.get((bd, comp, k), 0) > 0, (bd, comp, k)
+            print("cclm_shapes %d bit comp %d: cases by branch" % (bd, comp), {k: hits[(bd, comp, k)] for k in CCLM_BRANCHES})
+        assert all((bd, w, h, ("pattern", k)) in hits for (w, h) in legal for k in range(4)) and all((bd, w, h, ("kind", k)) in hits for (w, h) in legal for k in range(4))
+    np.savez_compressed(os.path.join(HERE, "cclm_shapes.npz"), meta=np.array(meta, np.int16), pred=np.concatenate(preds))
+    _report("cclm_shapes.npz", len(meta))
+
+
 if __name__ == "__main__":
     import sys
+    if len(sys.argv) > 1 and sys.argv[1] == "cclm_shapes":
+        gen_cclm_shapes(); sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "mip_range":
+        gen_mip_range(); sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "dist_range":
+        gen_dist_range(); sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "intra_shapes":
+        gen_intra_shapes(); sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "decision_helpers2":
         gen_decision_helpers2(); sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "trquant_range":
@@ -1269,4 +1605,5 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "cclm":
         gen_cclm(); sys.exit(0)      # added later: leaves the earlier fixtures (and the shared rng stream they used) untouched
     gen_transforms(); gen_dist(); gen_cabac(); gen_scan(); gen_intra(); gen_partition(); gen_trquant(); gen_bitstream(); gen_cclm(); gen_bitstream_cclm(); gen_trquant_mts(); gen_bitstream_mts(); gen_bitstream_mip(); gen_chroma_qp(); gen_deblock(); gen_mip(); gen_depquant(); gen_bitstream_dq(); gen_lfnst(); gen_bitstream_lfnst(); gen_bitstream_jccr(); gen_ict(); gen_decision_helpers(); gen_ts(); gen_bitstream_ts(); gen_isp(); gen_bitstream_isp(); gen_lmcs(); gen_bitstream_wpp(); gen_lmcs_analysis(); gen_sao(); gen_alf(); gen_trquant_range()
+    gen_intra_shapes(); gen_cclm_shapes(); gen_mip_range(); gen_dist_range()      # seeds of their own: the order does not matter
     print("done")

@@ -387,3 +387,47 @@ def sao_decide(stats, w, h, bit_depth, lambdas, slice_qp=32, tile_cols=1, tile_r
 
 SAO_CASES = ((128, 128, 8, 1, 1, 1, 0, 41), (256, 256, 8, 1, 1, 1, 0, 42), (384, 264, 10, 2, 2, 1, 0, 43), (320, 200, 8, 3, 2, 0, 0, 44), (512, 136, 10, 4, 1, 0, 1, 45), (200, 392, 8, 1, 3, 0, 0, 46))
 # (width, height, bit depth, tile columns, tile rows, filters across tile borders, log2 offset scale, seed)
+
+
+# ---- inputs of the leaf fixtures intra_shapes_*.npz / cclm_shapes.npz (tests/golden/make_golden.py): the fixtures hold only meta rows and the reference's predictions; the
+# pictures and the coded maps are regenerated from these two functions by the generator and by the tests
+LEAF_PIC = 192             # luma width and height of the 4:2:0 pictures
+
+
+def leaf_picture(bit_depth, pattern):
+    """three int16 planes: 0 samples alternating 0 / max with period 1 (horizontally in the upper half of a plane, vertically in the lower half, shifted by one sample every 8 rows /
+    columns so that the reference lines of every block see it), 1 squares of 24 x 24 samples of 0 and max (a step edge every 24 samples in both directions), 2 uniform full-range
+    noise, 3 a luma plane that is flat except for steps of +-1 under the alternating chroma of pattern 0 (CCLM: luma differences of 0 and 1 against chroma differences of max)"""
+    mx = (1 << bit_depth) - 1
+    planes = []
+    for c in range(3):
+        n = LEAF_PIC >> (c > 0)
+        yy, xx = np.mgrid[0:n, 0:n]
+        if pattern == 1:
+            p = ((xx // 24 + yy // 24) & 1) * mx
+        elif pattern == 2:
+            p = np.random.default_rng(7100 + 10 * bit_depth + c).integers(0, mx + 1, (n, n))
+        elif pattern == 3 and c == 0:
+            p = (1 << (bit_depth - 1)) + (xx // 12 + yy // 20) % 3 - 1
+        else:
+            p = np.where(yy < n // 2, (xx + yy // 8) & 1, (yy + xx // 8) & 1) * mx
+        planes.append(np.ascontiguousarray(p.astype(np.int16)))
+    return planes
+
+
+def leaf_coded_map(x, y, w, h, kind):
+    """which 8 x 8 luma units count as coded around the block (x, y, w, h) in luma samples (uint8 [24, 24]; units that touch the block never do): kind 0 exactly the causal
+    region (everything above the block's first row, and left of it down to its last row), 1 only units that lie entirely above or entirely left (left ones down to twice the height),
+    2 a seeded 60 % subset of those above or left down to twice the height, 3 everything above or left"""
+    n = LEAF_PIC // 8
+    py, px = np.mgrid[0:n, 0:n] * 8
+    inside = (px < x + w) & (px + 8 > x) & (py < y + h) & (py + 8 > y)
+    if kind == 0:
+        c = (py < y) | ((py < y + h) & (px < x))
+    elif kind == 1:
+        c = (py + 8 <= y) | ((px + 8 <= x) & (py < y + 2 * h))
+    elif kind == 2:
+        c = (np.random.default_rng([x, y, w, h]).random((n, n)) < 0.6) & (((py < y + 2 * h) & (px < x)) | (py < y))
+    else:
+        c = (py < y) | (px < x)
+    return np.ascontiguousarray((c & ~inside).astype(np.uint8))

@@ -397,6 +397,122 @@ def test_emulated_leaf_operators_match_reference(emu_so):
     assert _range_isp_tu(emu_so, 24) == 24
 
 
+# ---- every block shape, picture edges, range edges (tests/golden/intra_shapes_*.npz, cclm_shapes.npz, mip_range.npz, dist_range.npz) ----
+def _shape_slice(cases, limit, need):
+    """every case, or (CPU emulation) `limit` small blocks spread evenly plus the first case that satisfies each predicate of `need`"""
+    if not limit:
+        return cases
+    small = [c for c in cases if c["w"] * c["h"] <= 256]
+    pick = small[::max(1, len(small) // limit)][:limit]
+    for f in need:
+        pick.append(next(c for c in cases if f(c) and not any(c is q for q in pick)))
+    return pick
+
+
+def _shapes(lib, name, bd, limit=None, need=()):
+    """vvcx_intra_pred_batch on the cases of a shape fixture at one bit depth: one call per (picture, coded map), every prediction bit exact"""
+    import oracle_lib as O
+    from test_oracle_golden import _shape_cases, _leaf_planes
+    cases = _shape_slice([c for c in _shape_cases(name) if c["bd"] == bd], limit, need)
+    groups = {}
+    for c in cases:
+        groups.setdefault((c["pattern"], c["kind"], c["x"], c["y"], c["w"], c["h"]), []).append(c)
+    enc = pkg.VvcxEncoder(O.LEAF_PIC, O.LEAF_PIC, bd, lib_path=lib)
+    n = 0
+    for (pattern, kind, x, y, w, h), cs in groups.items():
+        reco = [p.astype(np.uint8 if bd == 8 else np.uint16) for p in _leaf_planes(bd, pattern)]
+        coded = np.repeat(np.repeat(O.leaf_coded_map(x, y, w, h, kind), 2, axis=0), 2, axis=1)            # 8x8 luma -> 4x4 units
+        pc = np.zeros(len(cs), pkg.PRED_CASE_DTYPE)
+        for k, c in enumerate(cs):
+            sh = 1 if c["comp"] else 0
+            pc[k] = (c["comp"], x >> sh, y >> sh, w >> sh, h >> sh, c["mode"], c["mrl"])
+        preds = enc.intra_pred_batch(reco, [coded, coded], pc)
+        for c, got in zip(cs, preds):
+            assert np.array_equal(got.ravel(), c["pred"]), {k: v for k, v in c.items() if k != "pred"}
+            n += 1
+    enc.close()
+    return n
+
+
+def _remap_edge(r, tall, remapped):
+    """luma cases of aspect ratio 2^r at the edge of getWideAngle's substitution: the last mode it remaps (2 + modeShift - 1 for wide blocks, mirrored for tall ones) or the
+    first it leaves alone; a wrong modeShift entry for that ratio moves one of the two"""
+    m = (0, 6, 10, 12, 14, 15)[r] + (1 if remapped else 2)
+    return lambda c: c["comp"] == 0 and ((c["h"], c["w"]) if tall else (c["w"], c["h"])) == (c["h" if tall else "w"], c["h" if tall else "w"] >> r) and c["mode"] == (68 - m if tall else m)
+
+
+INTRA_NEED = (lambda c: c["x"] == 0 and c["y"] == 0, lambda c: c["mrl"] == 3, lambda c: c["comp"] == 2 and c["h"] == 4) + tuple(
+    _remap_edge(r, tall, remapped) for r in (1, 2, 3, 4) for tall in (0, 1) for remapped in (1, 0))
+CCLM_NEED = (lambda c: c["mode"] == 67, lambda c: c["mode"] == 68, lambda c: c["mode"] == 69, lambda c: c["w"] * c["h"] == 64 * 64 and c["x"] > 0 and c["y"] > 0)      # the last: luma kept in the scratch slice
+
+
+def _mip_range(lib, bd, step=1):
+    vv = importlib.import_module(PKGNAME + ".vvcx")
+    g = np.load(os.path.join(G, "mip_range.npz"))
+    meta = g["meta"].astype(np.int64)
+    ro = np.concatenate([[0], np.cumsum(meta[:, 1] + meta[:, 2])]); po = np.concatenate([[0], np.cumsum(meta[:, 1] * meta[:, 2])])
+    idx = [i for i in range(len(meta)) if meta[i, 0] == bd][::step]
+    cases = np.stack([meta[idx, 1], meta[idx, 2], meta[idx, 3], meta[idx, 0]], axis=1).astype(np.int32)
+    refs = np.concatenate([g["refs"][ro[i]:ro[i + 1]] for i in idx]); exp = [g["preds"][po[i]:po[i + 1]] for i in idx]
+    got = vv.mip_pred_batch(cases, refs, lib_path=lib)
+    off = 0
+    for i, e in zip(idx, exp):
+        assert np.array_equal(got[off:off + len(e)], e), tuple(meta[i]); off += len(e)
+    return len(idx)
+
+
+def _dist_range(lib, bd, shapes=None):
+    """all patterns of a shape in one launch (one workgroup per pair of blocks)"""
+    from test_oracle_golden import _dist_range_cases
+    groups = {}
+    for c in _dist_range_cases():
+        if c[2] == bd and (shapes is None or (c[0], c[1]) in shapes):
+            groups.setdefault((c[0], c[1]), []).append(c)
+    n = 0
+    for (w, h), cs in groups.items():
+        got = pkg.distortion_batch(np.concatenate([c[7] for c in cs]), np.concatenate([c[8] for c in cs]), w, h, lib_path=lib)
+        for c, r in zip(cs, got):
+            assert (int(r[0]), int(r[1]), int(r[2])) == (c[4], c[3], c[5]), ("sad, satd, sse", w, h, bd, "pattern", c[6])
+            n += 1
+    return n
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bd", [8, 10])
+def test_gpu_intra_prediction_matches_reference_at_every_shape_and_range_edge(bd):
+    assert _shapes(None, "intra_shapes_%d" % bd, bd) == 4957
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bd", [8, 10])
+def test_gpu_cclm_prediction_matches_reference_at_every_shape_and_parameter_branch(bd):
+    """cclm_prepare + cclm_params + chroma_pred_wave, as the chroma search sets them up, through modes 67 / 68 / 69 of vvcx_intra_pred_batch"""
+    assert _shapes(None, "cclm_shapes", bd) == 1596
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bd", [8, 10])
+def test_gpu_mip_prediction_matches_reference_on_saturated_lines(bd):
+    assert _mip_range(None, bd) == 257
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bd", [8, 10])
+def test_gpu_distortion_matches_reference_at_the_ends_of_the_range(bd):
+    assert _dist_range(None, bd) == 324
+
+
+def test_emulated_leaf_operators_match_reference_at_shapes_and_range_edges(emu_so):
+    """slices of the shape and range fixtures through the CPU emulation of the same sources: small blocks spread over the fixtures plus the corner without neighbours, MRL 3, the
+    two modes at the edge of the wide-angle substitution for every aspect ratio and orientation, a chroma block two samples high, every CCLM mode, a CCLM block that keeps its luma in the scratch slice, MIP on every fourth case,
+    every saturated SAD / SATD pattern on each Hadamard tile shape"""
+    for bd in (8, 10):
+        assert _shapes(emu_so, "intra_shapes_%d" % bd, bd, 30, INTRA_NEED) == 30 + len(INTRA_NEED)
+        assert _shapes(emu_so, "cclm_shapes", bd, 24, CCLM_NEED) == 24 + len(CCLM_NEED)
+        assert _mip_range(emu_so, bd, 4) == 65
+        assert _dist_range(emu_so, bd, ((2, 2), (2, 16), (4, 4), (8, 4), (4, 8), (8, 8), (16, 8), (8, 16), (64, 16))) == 9 * 9
+
+
 @pytest.mark.gpu
 def test_mip_prediction():
     """Device MIP prediction (vvcx_mip.hip: one wave per block, closed-form up-sampling) against MatrixIntraPrediction of the reference:

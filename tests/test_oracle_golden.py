@@ -892,3 +892,117 @@ def test_full_range_isp_sub_partition_transform_path_against_the_reference():
         assert np.array_equal(lev, c["lev"]), ("levels", key)
         if a:
             assert np.array_equal(out, c["out"]), ("resi", key)
+
+
+# ---- leaf fixtures at every block shape and at the range edges (make_golden.py intra_shapes / cclm_shapes / mip_range / dist_range).  The fixtures hold meta rows and the
+# reference's outputs; O.leaf_picture / O.leaf_coded_map regenerate the pictures and the neighbourhoods
+_leaf_cache = {}
+
+
+def _leaf_planes(bd, pattern):
+    if ("pic", bd, pattern) not in _leaf_cache:
+        _leaf_cache[("pic", bd, pattern)] = O.leaf_picture(bd, pattern)
+    return _leaf_cache[("pic", bd, pattern)]
+
+
+def _shape_cases(name):
+    """cases of intra_shapes_8 / intra_shapes_10 / cclm_shapes as dicts: bd, pattern (picture), kind (neighbourhood rule), comp, x, y, w, h (luma samples), mode, mrl, pred"""
+    if name not in _leaf_cache:
+        g = np.load(os.path.join(G, name + ".npz"))
+        meta, pred = g["meta"].astype(np.int64), g["pred"].astype(np.int16)
+        if name == "cclm_shapes":
+            meta = np.concatenate([meta, np.zeros((len(meta), 1), np.int64)], axis=1)
+        else:
+            meta = np.concatenate([np.full((len(meta), 1), int(name.rsplit("_", 1)[1])), meta], axis=1)
+        out, off = [], 0
+        for m in meta.tolist():
+            c = dict(zip(("bd", "pattern", "kind", "comp", "x", "y", "w", "h", "mode", "mrl"), m))
+            n = (c["w"] * c["h"]) >> (2 if c["comp"] else 0)
+            c["pred"] = pred[off:off + n]; off += n
+            out.append(c)
+        assert off == len(pred)
+        _leaf_cache[name] = out
+    return _leaf_cache[name]
+
+
+@pytest.mark.parametrize("bd", [8, 10])
+def test_intra_prediction_at_every_shape_position_and_range_edge(bd):
+    """orc_fill_ref_samples + orc_filter_ref_samples + orc_pred_intra against initIntraPatternChType + predIntraAng on the full-range pictures: every luma and chroma shape, the
+    picture's edges and corner, the first row of a CTU, MRL 1 / 3, wide angles of every aspect ratio (tests/golden/intra_shapes_*.npz)"""
+    L = O.lib()
+    n = 0
+    ref_unf = np.zeros(4 * 300 * 300, np.int16); ref_flt = np.zeros_like(ref_unf)
+    for c in _shape_cases("intra_shapes_%d" % bd):
+        ch = 1 if c["comp"] else 0
+        plane = _leaf_planes(bd, c["pattern"])[c["comp"]]
+        avail = _avail_map(O.leaf_coded_map(c["x"], c["y"], c["w"], c["h"], c["kind"]), O.LEAF_PIC, O.LEAF_PIC)
+        cx, cy, cw, chh = c["x"] >> ch, c["y"] >> ch, c["w"] >> ch, c["h"] >> ch
+        L.orc_fill_ref_samples(P(plane), plane.shape[1], plane.shape[1], plane.shape[0], P(avail), avail.shape[1], 1 if ch else 2, 1, cx, cy, cw, chh, c["mrl"], bd, P(ref_unf))
+        L.orc_filter_ref_samples(P(ref_unf), P(ref_flt), cw, chh, c["mrl"])
+        pred = np.zeros(cw * chh, np.int16)
+        L.orc_pred_intra(P(ref_unf), P(ref_flt), cw, chh, 0 if ch else 1, c["mode"], c["mrl"], bd, P(pred), cw)
+        assert np.array_equal(pred, c["pred"]), {k: v for k, v in c.items() if k != "pred"}
+        n += 1
+    assert n == 4957
+
+
+def test_cclm_prediction_at_every_shape_position_and_parameter_branch():
+    """the CCLM trio against xGetLumaRecPixels + xGetLMParameters + predIntraChromaLM: every chroma shape (heights of 2 included), first row of a CTU and not, MDLM with and
+    without its extension, and every branch of the parameter derivation (tests/golden/cclm_shapes.npz; the generator asserts the branches)"""
+    L = O.lib()
+    n = 0
+    ref = np.zeros(4 * 300 * 300, np.int16)
+    tstride = 2 * 64 + 2
+    for c in _shape_cases("cclm_shapes"):
+        bd = c["bd"]
+        reco = _leaf_planes(bd, c["pattern"])
+        avail = _avail_map(O.leaf_coded_map(c["x"], c["y"], c["w"], c["h"], c["kind"]), O.LEAF_PIC, O.LEAF_PIC)
+        cx, cy, cw, chh = c["x"] // 2, c["y"] // 2, c["w"] // 2, c["h"] // 2
+        plane = reco[c["comp"]]
+        L.orc_fill_ref_samples(P(plane), plane.shape[1], plane.shape[1], plane.shape[0], P(avail), avail.shape[1], 1, 1, cx, cy, cw, chh, 0, bd, P(ref))
+        tmp = np.zeros(tstride * tstride, np.int16); info = np.zeros(4, np.int32)
+        L.orc_cclm_luma(P(reco[0]), O.LEAF_PIC, P(avail), avail.shape[1], 1, O.LEAF_PIC // 2, O.LEAF_PIC // 2, cx, cy, cw, chh, int(c["mode"] != 67), P(info), P(tmp), tstride)
+        a = C.c_int(); b = C.c_int(); sh = C.c_int()
+        L.orc_cclm_params(P(tmp), tstride, P(ref), cw, chh, c["mode"], P(info), bd, C.byref(a), C.byref(b), C.byref(sh))
+        pred = np.zeros(cw * chh, np.int16)
+        L.orc_pred_cclm(P(tmp), tstride, a.value, b.value, sh.value, bd, cw, chh, P(pred), cw)
+        assert np.array_equal(pred, c["pred"]), ({k: v for k, v in c.items() if k != "pred"}, a.value, b.value, sh.value, info)
+        n += 1
+    assert n == 3192
+
+
+def test_matrix_based_intra_prediction_from_saturated_and_alternating_lines():
+    """orc_pred_mip against MatrixIntraPrediction on reference lines that are all 0, all max, alternating, stepped and full-range noise (tests/golden/mip_range.npz)"""
+    L = O.lib()
+    g = np.load(os.path.join(G, "mip_range.npz"))
+    ro = po = n = 0
+    for (bd, w, h, mode, kt, kl) in g["meta"].tolist():
+        top = np.ascontiguousarray(g["refs"][ro:ro + w]); left = np.ascontiguousarray(g["refs"][ro + w:ro + w + h]); ro += w + h
+        exp = g["preds"][po:po + w * h]; po += w * h
+        out = np.zeros(w * h, np.int16)
+        L.orc_pred_mip(P(top), P(left), w, h, mode, bd, P(out))
+        assert np.array_equal(out, exp), (bd, w, h, mode, kt, kl)
+        n += 1
+    assert n == 514
+
+
+def _dist_range_cases():
+    """(w, h, bd, satd, sad, sse, pattern, a, b) of tests/golden/dist_range.npz"""
+    g = np.load(os.path.join(G, "dist_range.npz"))
+    out, off = [], 0
+    for (w, h, bd, had, sad, sse, k) in g["rows"].tolist():
+        out.append((w, h, bd, had, sad, sse, k, np.ascontiguousarray(g["a"][off:off + w * h]), np.ascontiguousarray(g["b"][off:off + w * h]))); off += w * h
+    return out
+
+
+def test_distortion_at_the_ends_of_the_range():
+    """orc_sad / orc_satd / orc_sse against RdCost on blocks whose difference is +-(2^bd - 1) everywhere (one sign, Hadamard basis functions of the tile, checkerboard, random
+    signs), on one differing sample and on equal blocks; two-sample-wide blocks included (tests/golden/dist_range.npz)"""
+    L = O.lib()
+    n = 0
+    for (w, h, bd, had, sad, sse, k, a, b) in _dist_range_cases():
+        assert L.orc_satd(P(a), w, P(b), w, w, h) == had, ("satd", w, h, bd, k)
+        assert L.orc_sad(P(a), w, P(b), w, w, h) == sad, ("sad", w, h, bd, k)
+        assert L.orc_sse(P(a), w, P(b), w, w, h) == sse, ("sse", w, h, bd, k)
+        n += 1
+    assert n == 648
