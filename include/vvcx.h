@@ -204,7 +204,7 @@ int  vvcx_lmcs_analyze_device(const void *const org[3], const int stride[3], int
 int  vvcx_lmcs_tables(vvcx_handle *h, int16_t *fwd, int16_t *inv, int32_t pivot[17], int32_t chroma_scale[16]);
 /* ≙ LoopFilter::loopFilterPic (CL/LoopFilter.cpp:153; called from EncGOP after the slices of a picture are compressed): in-loop deblocking
  * of every bound picture, in place on its reconstruction planes; offsets = cfg LoopFilterBetaOffset_div2 / LoopFilterTcOffset_div2.
- * Every CTU of the pictures must have been compressed.  SAO and ALF, which follow in the reference, are not built. */
+ * Every CTU of the pictures must have been compressed.  SAO and ALF follow in the reference: vvcx_sao_bound_frames and vvcx_alf_bound_frames below. */
 int  vvcx_deblock_bound_frames(vvcx_handle *h, int beta_offset_div2, int tc_offset_div2, void *hip_stream);
 float vvcx_last_deblock_ms(const vvcx_handle *h);
 /* ≙ SampleAdaptiveOffset::SAOProcess(cs, saoBlkParams) (CL/SampleAdaptiveOffset.cpp:617-670): sample adaptive offset on every bound (completely coded) picture, in place on

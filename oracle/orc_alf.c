@@ -22,6 +22,10 @@
 
 static int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
 
+/* Branch counters of orc_alf_picture (ORC_ALF_*, vvc_oracle.h) since the last read-out: see orc_deblock_counters.  Not thread safe. */
+static int64_t ALF_CNT[ORC_ALF_COUNTERS];
+void orc_alf_counters(int64_t *out) { memcpy(out, ALF_CNT, sizeof ALF_CNT); memset(ALF_CNT, 0, sizeof ALF_CNT); }
+
 /* the clipping values of create() 633-654: luma round(2^(bd (4 - i) / 4)), chroma 2^bd, then round(2^(bd - 8 + 8 (2 - (i - 1)) / 3)) */
 int orc_alf_clip_value(int chroma, int bit_depth, int idx)
 {
@@ -91,16 +95,32 @@ static void classify(const plane_t *s, int X, int Y, int bit_depth, int ctuH, in
 }
 
 static int clip2(int clip, int ref, int v0, int v1) { return clampi(v0 - ref, -clip, clip) + clampi(v1 - ref, -clip, clip); }
+/* one pair of taps of a sample: which clipping index its value is (idx_of: the four values of the component and bit depth) and whether it cut a difference */
+static void count_clip(const int *idx_of, int clip, int ref, int v0, int v1)
+{
+  for (int i = 0; i < 4; i++) if (idx_of[i] == clip) {
+    ALF_CNT[ORC_ALF_CLIP_IDX_USED + i]++;
+    if (abs(v0 - ref) > clip || abs(v1 - ref) > clip) ALF_CNT[ORC_ALF_CLIP_IDX_CUT + i]++;
+    break;
+  }
+}
 
 /* one sample of the 7 x 7 (luma) / 5 x 5 (chroma) diamond; co / cl in the order of the block's transpose; yVb: the sample's row inside its CTU */
-static int filter_sample(const plane_t *s, int x, int y, int chroma, const int *co, const int *cl, int yVb, int vbPos, int maxv)
+static int filter_sample(const plane_t *s, int x, int y, int chroma, const int *co, const int *cl, int yVb, int vbPos, int maxv, const int *idx_of)
 {
   int d1 = 1, d2 = 2, d3 = 3;                               /* row distances of the three tap rows on either side (the same above and below) */
   const int reach = chroma ? 2 : 4;
-  if (yVb < vbPos && yVb >= vbPos - reach) { const int room = vbPos - 1 - yVb; d1 = d1 < room ? d1 : room; d2 = d2 < room ? d2 : room; d3 = d3 < room ? d3 : room; }
-  else if (yVb >= vbPos && yVb <= vbPos + reach - 1) { const int room = yVb - vbPos; d1 = d1 < room ? d1 : room; d2 = d2 < room ? d2 : room; d3 = d3 < room ? d3 : room; }
+  if (yVb < vbPos && yVb >= vbPos - reach) { const int room = vbPos - 1 - yVb; d1 = d1 < room ? d1 : room; d2 = d2 < room ? d2 : room; d3 = d3 < room ? d3 : room; ALF_CNT[(chroma ? ORC_ALF_VB_CHROMA : ORC_ALF_VB_LUMA) + room]++; }
+  else if (yVb >= vbPos && yVb <= vbPos + reach - 1) { const int room = yVb - vbPos; d1 = d1 < room ? d1 : room; d2 = d2 < room ? d2 : room; d3 = d3 < room ? d3 : room; ALF_CNT[(chroma ? ORC_ALF_VB_CHROMA : ORC_ALF_VB_LUMA) + room]++; }
   const int cur = px(s, x, y);
   int sum = 0;
+  if (!chroma) {
+    const int dy[12] = { d3, d2, d2, d2, d1, d1, d1, d1, d1, 0, 0, 0 }, dx[12] = { 0, 1, 0, -1, 2, 1, 0, -1, -2, 3, 2, 1 };
+    for (int i = 0; i < 12; i++) count_clip(idx_of, cl[i], cur, px(s, x + dx[i], y + dy[i]), px(s, x - dx[i], y - dy[i]));
+  } else {
+    const int dy[6] = { d2, d1, d1, d1, 0, 0 }, dx[6] = { 0, 1, 0, -1, 2, 1 };
+    for (int i = 0; i < 6; i++) count_clip(idx_of, cl[i], cur, px(s, x + dx[i], y + dy[i]), px(s, x - dx[i], y - dy[i]));
+  }
   if (!chroma) {
     sum += co[0] * clip2(cl[0], cur, px(s, x, y + d3), px(s, x, y - d3));
     sum += co[1] * clip2(cl[1], cur, px(s, x + 1, y + d2), px(s, x - 1, y - d2));
@@ -122,7 +142,10 @@ static int filter_sample(const plane_t *s, int x, int y, int chroma, const int *
     sum += co[4] * clip2(cl[4], cur, px(s, x + 2, y), px(s, x - 2, y));
     sum += co[5] * clip2(cl[5], cur, px(s, x + 1, y), px(s, x - 1, y));
   }
-  return clampi(((sum + 64) >> 7) + cur, 0, maxv);
+  const int r = ((sum + 64) >> 7) + cur;
+  if (r < 0) ALF_CNT[ORC_ALF_CLIP_0]++;
+  if (r > maxv) ALF_CNT[ORC_ALF_CLIP_MAX]++;
+  return clampi(r, 0, maxv);
 }
 
 /* The picture filtered in place.  sets: n_sets luma tables [25][13] of coefficients / clipping values (filter set 16 + k), alts: n_alt chroma tables [7];
@@ -141,6 +164,8 @@ int orc_alf_picture(int w, int h, int bit_depth, int n_sets, const int16_t *luma
     int16_t *src = (int16_t *) malloc((size_t) pw * ph * sizeof(int16_t));
     memcpy(src, planes[c], (size_t) pw * ph * sizeof(int16_t));
     const plane_t S = { src, pw, ph };
+    int idx_of[4];
+    for (int i = 0; i < 4; i++) idx_of[i] = orc_alf_clip_value(c != 0, bit_depth, i);
     for (int by = 0; by < ph; by += 4) for (int bx = 0; bx < pw; bx += 4) {
       const int a = (by / ctuS) * cw + bx / ctuS;
       const orc_alf_ctu *u = &ctu[a];
@@ -150,6 +175,8 @@ int orc_alf_picture(int w, int h, int bit_depth, int n_sets, const int16_t *luma
       if (c == 0) {
         int cls, tr;
         classify(&S, bx, by, bit_depth, ctuS, vbPos, &cls, &tr);
+        ALF_CNT[ORC_ALF_TRANSPOSE + tr]++;
+        if (u->set >= 0 && u->set < 16) ALF_CNT[ORC_ALF_SET_CLASS + u->set * 25 + cls]++;
         if (cls_out) cls_out[(size_t) (by >> 2) * (w >> 2) + (bx >> 2)] = (uint8_t) (cls | (tr << 5));
         const int set = u->set;
         if (set < 0 || set >= 16 + n_sets) { free(src); return -1; }
@@ -164,7 +191,7 @@ int orc_alf_picture(int w, int h, int bit_depth, int n_sets, const int16_t *luma
         for (int i = 0; i < 6; i++) { co[i] = chroma_coeff[t * 7 + i]; cl[i] = chroma_clip[t * 7 + i]; }
       }
       for (int yy = by; yy < by + 4; yy++) for (int xx = bx; xx < bx + 4; xx++)
-        planes[c][(size_t) yy * pw + xx] = (int16_t) filter_sample(&S, xx, yy, c != 0, co, cl, yy & (ctuS - 1), vbPos, maxv);
+        planes[c][(size_t) yy * pw + xx] = (int16_t) filter_sample(&S, xx, yy, c != 0, co, cl, yy & (ctuS - 1), vbPos, maxv, idx_of);
     }
     free(src);
   }

@@ -17,6 +17,18 @@ static const uint16_t TC_TABLE[66] = { 0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,3,4,4
 static const uint8_t BETA_TABLE[64] = { 0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,0,6,7,8,9,10,11,12,13,14,15,16,17,18,20,22,24,26,28,30,32,34,36,38,40,42,44,46,48,50,52,54,56,58,60,62,64,66,68,70,72,74,76,78,80,82,84,86,88 };
 
 static int clip3(int lo, int hi, int v) { return v < lo ? lo : v > hi ? hi : v; }
+
+/* Branch counters (ORC_DB_*, vvc_oracle.h): which decisions the segments filtered since the last read-out took.  They let a fixture's generator and its test assert that the
+ * inputs reach every branch; they say the same of the reference wherever the test also finds the oracle's output equal to the reference's.  Not thread safe. */
+static int64_t DB_CNT[ORC_DB_COUNTERS];
+void orc_deblock_counters(int64_t *out) { memcpy(out, DB_CNT, sizeof DB_CNT); memset(DB_CNT, 0, sizeof DB_CNT); }
+/* the weak filters' clip to the sample range, counted per sample */
+static int clip_range(int mx, int v, int chroma)
+{
+  if (v < 0) { DB_CNT[chroma ? ORC_DB_C_CLIP_0 : ORC_DB_WEAK_CLIP_0]++; return 0; }
+  if (v > mx) { DB_CNT[chroma ? ORC_DB_C_CLIP_MAX : ORC_DB_WEAK_CLIP_MAX]++; return mx; }
+  return v;
+}
 static int iabs_(int v) { return v < 0 ? -v : v; }
 static int calc_dp(const int16_t *s, int o) { return iabs_(s[-o * 3] - 2 * s[-o * 2] + s[-o]); }
 static int calc_dq(const int16_t *s, int o) { return iabs_(s[0] - 2 * s[o] + s[o * 2]); }
@@ -73,12 +85,12 @@ static void pel_filter_luma(int16_t *s, int o, int tc, int sw, int thrCut, int s
   int delta = (9 * (m4 - m3) - 3 * (m5 - m2) + 8) >> 4;
   if (iabs_(delta) < thrCut) {
     delta = clip3(-tc, tc, delta);
-    s[-o] = (int16_t) clip3(0, mx, m3 + delta);
-    s[0]  = (int16_t) clip3(0, mx, m4 - delta);
+    s[-o] = (int16_t) clip_range(mx, m3 + delta, 0);
+    s[0]  = (int16_t) clip_range(mx, m4 - delta, 0);
     const int tc2 = tc >> 1;
-    if (secondP) s[-o * 2] = (int16_t) clip3(0, mx, m2 + clip3(-tc2, tc2, ((((m1 + m3 + 1) >> 1) - m2 + delta) >> 1)));
-    if (secondQ) s[o]      = (int16_t) clip3(0, mx, m5 + clip3(-tc2, tc2, ((((m6 + m4 + 1) >> 1) - m5 - delta) >> 1)));
-  }
+    if (secondP) s[-o * 2] = (int16_t) clip_range(mx, m2 + clip3(-tc2, tc2, ((((m1 + m3 + 1) >> 1) - m2 + delta) >> 1)), 0);
+    if (secondQ) s[o]      = (int16_t) clip_range(mx, m5 + clip3(-tc2, tc2, ((((m6 + m4 + 1) >> 1) - m5 - delta) >> 1)), 0);
+  } else DB_CNT[ORC_DB_WEAK_THRCUT]++;
 }
 static void pel_filter_chroma(int16_t *s, int o, int tc, int sw, int mx)
 {
@@ -92,8 +104,8 @@ static void pel_filter_chroma(int16_t *s, int o, int tc, int sw, int mx)
     s[o * 2]  = (int16_t) clip3(m6 - tc, m6 + tc, (m3 + m4 + m5 + 2 * m6 + 3 * m7 + 4) >> 3);
   } else {
     const int delta = clip3(-tc, tc, ((((m4 - m3) << 2) + m2 - m5 + 4) >> 3));
-    s[-o] = (int16_t) clip3(0, mx, m3 + delta);
-    s[0]  = (int16_t) clip3(0, mx, m4 - delta);
+    s[-o] = (int16_t) clip_range(mx, m3 + delta, 1);
+    s[0]  = (int16_t) clip_range(mx, m4 - delta, 1);
   }
 }
 static int tc_of(int idx, int bd) { return bd < 10 ? ((TC_TABLE[idx] + 2) >> (10 - bd)) : (TC_TABLE[idx] << (bd - 10)); }
@@ -106,6 +118,8 @@ void orc_deblock_luma_segment(int16_t *s, int o, int step, int sizeP, int sizeQ,
   if (sizeP <= 4 || sizeQ <= 4) lenP = lenQ = 1;
   else { lenQ = sizeQ >= 32 ? 7 : 3; lenP = sizeP >= 32 ? 7 : 3; }
   int pLarge = lenP > 3, qLarge = lenQ > 3;
+  if (lenP == 1) DB_CNT[ORC_DB_LEN_1]++;
+  if (ctuTop && pLarge) DB_CNT[ORC_DB_CTU_TOP]++;
   if (ctuTop) pLarge = 0;
   const int idxTC = clip3(0, 63 + 2, qp + 2 * (2 - 1) + (tc_off2 << 1)), idxB = clip3(0, 63, qp + (beta_off2 << 1));
   const int tc = tc_of(idxTC, bd), beta = BETA_TABLE[idxB] * (1 << (bd - 8));
@@ -121,9 +135,11 @@ void orc_deblock_luma_segment(int16_t *s, int o, int step, int sizeP, int sizeQ,
       const int fP = dpL < sideThr, fQ = dqL < sideThr;
       if (use_strong(s, o, 2 * d0L, beta, tc, pLarge, qLarge, lenP, lenQ) && use_strong(s + 3 * step, o, 2 * d3L, beta, tc, pLarge, qLarge, lenP, lenQ)) {
         longTap = 1;
+        DB_CNT[pLarge && qLarge ? ORC_DB_LONG_77 : pLarge ? ORC_DB_LONG_73 : ORC_DB_LONG_37]++;
         for (int i = 0; i < 4; i++) pel_filter_luma(s + i * step, o, tc, 1, thrCut, fP, fQ, mx, pLarge, qLarge, lenP, lenQ);
       }
     }
+    if (!longTap) DB_CNT[ORC_DB_LONG_FAILED]++;
   }
   if (!longTap) {
     const int d0 = dp0 + dq0, d3 = dp3 + dq3, dp = dp0 + dp3, dq = dq0 + dq3;
@@ -131,15 +147,18 @@ void orc_deblock_luma_segment(int16_t *s, int o, int step, int sizeP, int sizeQ,
       int fP = 0, fQ = 0, sw = 0;
       if (lenP > 1 && lenQ > 1) { fP = dp < sideThr; fQ = dq < sideThr; }
       if (lenP > 2 && lenQ > 2) sw = use_strong(s, o, 2 * d0, beta, tc, 0, 0, 0, 0) && use_strong(s + 3 * step, o, 2 * d3, beta, tc, 0, 0, 0, 0);
+      DB_CNT[sw ? ORC_DB_SHORT_STRONG : ORC_DB_WEAK_00 + 2 * fP + fQ]++;
       for (int i = 0; i < 4; i++) pel_filter_luma(s + i * step, o, tc, sw, thrCut, fP, fQ, mx, 0, 0, 0, 0);
-    }
+    } else DB_CNT[ORC_DB_NOT_FILTERED]++;
   }
 }
 /* one 2-line segment of a chroma edge of one component (4:2:0): sizes in chroma samples; qp = mapped chroma QP (+ offset, clipped to 0..63) */
 void orc_deblock_chroma_segment(int16_t *s, int o, int step, int sizeP, int sizeQ, int ctuTop, int qp, int bd, int beta_off2, int tc_off2)
 {
   int large = sizeP >= 8 && sizeQ >= 8;
+  if (ctuTop && large) DB_CNT[ORC_DB_C_CTU_TOP]++;
   if (ctuTop) large = 0;
+  if (!large) DB_CNT[ORC_DB_C_NOT_LARGE]++;
   const int idxTC = clip3(0, 63 + 2, qp + 2 * (2 - 1) + (tc_off2 << 1));
   const int tc = tc_of(idxTC, bd), mx = (1 << bd) - 1;
   int useLong = 0;
@@ -150,8 +169,9 @@ void orc_deblock_chroma_segment(int16_t *s, int o, int step, int sizeP, int size
     if (d0 + d3 < beta) {
       useLong = 1;
       const int sw = use_strong(s, o, 2 * d0, beta, tc, 0, 0, 0, 0) && use_strong(s + step, o, 2 * d3, beta, tc, 0, 0, 0, 0);
+      DB_CNT[sw ? ORC_DB_C_LARGE_STRONG : ORC_DB_C_LARGE_WEAK]++;
       for (int i = 0; i < 2; i++) pel_filter_chroma(s + i * step, o, tc, sw, mx);
-    }
+    } else DB_CNT[ORC_DB_C_LARGE_NO_D]++;
   }
   if (!useLong) for (int i = 0; i < 2; i++) pel_filter_chroma(s + i * step, o, tc, 0, mx);
 }

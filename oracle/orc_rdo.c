@@ -2333,6 +2333,9 @@ int orc_deblock_frame(orc_enc *e, int beta_offset_div2, int tc_offset_div2)
 /* the same filter on a picture given as a CU table (rows of {ch, x, y, w, h, ispMode}, luma samples) and its planes (4:2:0, stride = plane width), so that the pin against
  * the reference's LoopFilter can cover CU tables no search produced (tests/golden/make_golden.py deblock: forced ISP splits) */
 int orc_deblock_table(int w, int h, int bd, int qp, int qp_cb, int qp_cr, const int *rows, int nrows, int16_t *y, int16_t *cb, int16_t *cr)
+{ return orc_deblock_table_offsets(w, h, bd, qp, qp_cb, qp_cr, 0, 0, rows, nrows, y, cb, cr); }
+/* ... with the slice's beta / tc offsets (qp_cb / qp_cr: the chroma QPs the edges are filtered at, PPS offsets included) */
+int orc_deblock_table_offsets(int w, int h, int bd, int qp, int qp_cb, int qp_cr, int beta_offset_div2, int tc_offset_div2, const int *rows, int nrows, int16_t *y, int16_t *cb, int16_t *cr)
 {
   const int uw = (w + 3) >> 2, uh = (h + 3) >> 2;
   unit_t *um[2] = { calloc((size_t) uw * uh, sizeof(unit_t)), calloc((size_t) uw * uh, sizeof(unit_t)) };
@@ -2346,7 +2349,7 @@ int orc_deblock_table(int w, int h, int bd, int qp, int qp_cb, int qp_cr, const 
   }
   int16_t *rec[3] = { y, cb, cr };
   const int stride[3] = { w, w >> 1, w >> 1 }, qpc[2] = { qp_cb, qp_cr };
-  dbk_picture(um[0], um[1], uw, uh, rec, stride, qp, qpc, bd, 1, 0, 0);
+  dbk_picture(um[0], um[1], uw, uh, rec, stride, qp, qpc, bd, 1, beta_offset_div2, tc_offset_div2);
   free(um[0]); free(um[1]);
   return 0;
 }

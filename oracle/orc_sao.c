@@ -18,6 +18,10 @@
 #include "orc_internal.h"
 
 static int sgn_(int v) { return (v > 0) - (v < 0); }
+
+/* Branch counters of orc_sao_picture (ORC_SAO_*, vvc_oracle.h), per sample since the last read-out: see orc_deblock_counters.  Not thread safe. */
+static int64_t SAO_CNT[ORC_SAO_COUNTERS];
+void orc_sao_counters(int64_t *out) { memcpy(out, SAO_CNT, sizeof SAO_CNT); memset(SAO_CNT, 0, sizeof SAO_CNT); }
 static int tile_of(int ctu, int n_ctus, int n_tiles) { int t = 0; for (int i = 0; i < n_tiles; i++) if (ctu >= (i * n_ctus) / n_tiles) t = i; return t; }
 
 /* prm: per CTU (raster) and component {mode 0 off / 1 new / 2 merge, type (new: 0..3 edge class 0 / 90 / 135 / 45 degrees, 4 band; merge: 0 left, 1 above),
@@ -60,18 +64,27 @@ int orc_sao_picture(int w, int h, int bit_depth, int tile_cols, int tile_rows, i
       const int16_t *o = &off[(size_t) (a * 3 + c) * 32];
       const int v = src[yy * pw + xx];
       int r;
-      if (t == 4) r = v + o[v >> (bit_depth - 5)];
-      else {
+      if (t == 4) {
+        const int band = v >> (bit_depth - 5), k = (band - prm[a * 3 + c].band) & 31;      /* (a merged CTU counts with its own band position: the fixtures' band CTUs are not merged) */
+        r = v + o[band];
+        if (prm[a * 3 + c].mode == 1 && k < 4) { SAO_CNT[ORC_SAO_BAND_K + k]++; if (band < prm[a * 3 + c].band) SAO_CNT[ORC_SAO_BAND_WRAP]++; }
+      } else {
         const int dx = t == 1 ? 0 : 1, dy = t == 0 ? 0 : 1;
         const int ax = t == 3 ? xx + 1 : xx - dx, ay = yy - dy, bx = t == 3 ? xx - 1 : xx + dx, by = yy + dy;      /* 45 degrees: above-right and below-left */
         int ok = ax >= 0 && ax < pw && ay >= 0 && ay < ph && bx >= 0 && bx < pw && by >= 0 && by < ph;
+        if (!ok) SAO_CNT[ORC_SAO_OUTSIDE_PICTURE]++;
         if (ok && !lf_across_tiles) {
           const int tx = tile_of(cx, cw, tile_cols), ty = tile_of(cy, ch, tile_rows);
           ok = tile_of(ax / cs, cw, tile_cols) == tx && tile_of(ay / cs, ch, tile_rows) == ty && tile_of(bx / cs, cw, tile_cols) == tx && tile_of(by / cs, ch, tile_rows) == ty;
+          if (!ok) SAO_CNT[ORC_SAO_OTHER_TILE]++;
         }
         if (!ok) continue;
-        r = v + o[2 + sgn_(v - src[ay * pw + ax]) + sgn_(v - src[by * pw + bx])];
+        const int k = 2 + sgn_(v - src[ay * pw + ax]) + sgn_(v - src[by * pw + bx]);
+        SAO_CNT[ORC_SAO_EDGE + t * 5 + k]++;
+        r = v + o[k];
       }
+      if (r < 0) SAO_CNT[ORC_SAO_CLIP_0]++;
+      if (r > mx) SAO_CNT[ORC_SAO_CLIP_MAX]++;
       planes[c][yy * pw + xx] = (int16_t) (r < 0 ? 0 : r > mx ? mx : r);
     }
     free(src);

@@ -130,6 +130,25 @@ int      orc_forest_predict_rows(orc_enc *e, const int32_t *rows, int n, int32_t
 int      orc_deblock_frame(orc_enc *e, int beta_offset_div2, int tc_offset_div2);
 /* the same filter on a CU table {ch, x, y, w, h, ispMode} (luma samples) and 4:2:0 planes with stride = plane width; qp_cb / qp_cr = mapped chroma QPs */
 int      orc_deblock_table(int w, int h, int bd, int qp, int qp_cb, int qp_cr, const int *rows, int nrows, int16_t *y, int16_t *cb, int16_t *cr);
+int      orc_deblock_table_offsets(int w, int h, int bd, int qp, int qp_cb, int qp_cr, int beta_offset_div2, int tc_offset_div2, const int *rows, int nrows, int16_t *y, int16_t *cb, int16_t *cr);
+/* Branch counters of the three loop filters: what the calls since the last read-out executed (read and reset; plain statics, not thread safe).  A fixture's generator and its
+ * test assert through them that the inputs reach every branch.
+ * Deblocking, luma per 4-line segment: no filter (d >= beta) | long filter by (lenP, lenQ) | long decision failed, short path taken | pLarge suppressed at a CTU top | short strong |
+ * weak by (fP, fQ) | per line: weak rejected by thrCut | per sample: weak result clipped at 0 / max | lenP = lenQ = 1.  Chroma per 2-line segment and component: large + strong |
+ * large + weak | large but d >= beta (the unconditional weak filter) | not large | large suppressed at a CTU top | per sample: weak result clipped at 0 / max */
+enum { ORC_DB_NOT_FILTERED, ORC_DB_LONG_77, ORC_DB_LONG_73, ORC_DB_LONG_37, ORC_DB_LONG_FAILED, ORC_DB_CTU_TOP, ORC_DB_SHORT_STRONG, ORC_DB_WEAK_00, ORC_DB_WEAK_01, ORC_DB_WEAK_10, ORC_DB_WEAK_11,
+       ORC_DB_WEAK_THRCUT, ORC_DB_WEAK_CLIP_0, ORC_DB_WEAK_CLIP_MAX, ORC_DB_LEN_1, ORC_DB_C_LARGE_STRONG, ORC_DB_C_LARGE_WEAK, ORC_DB_C_LARGE_NO_D, ORC_DB_C_NOT_LARGE, ORC_DB_C_CTU_TOP,
+       ORC_DB_C_CLIP_0, ORC_DB_C_CLIP_MAX, ORC_DB_COUNTERS };
+void     orc_deblock_counters(int64_t *out /* [ORC_DB_COUNTERS] */);
+/* SAO per sample: edge type t (0..3) with class k (0..4, 2 = none) at ORC_SAO_EDGE + 5 t + k | band offset k (0..3) | ... in a band below the band position (the wrap past
+ * band 31) | result clipped at 0 / max | an edge neighbour outside the picture | ... in another tile */
+enum { ORC_SAO_EDGE = 0, ORC_SAO_BAND_K = 20, ORC_SAO_BAND_WRAP = 24, ORC_SAO_CLIP_0, ORC_SAO_CLIP_MAX, ORC_SAO_OUTSIDE_PICTURE, ORC_SAO_OTHER_TILE, ORC_SAO_COUNTERS };
+void     orc_sao_counters(int64_t *out /* [ORC_SAO_COUNTERS] */);
+/* ALF per sample: result clipped at 0 / max | per pair of taps: clipping index i (0..3) used | ... and it cut a difference | samples whose tap rows a virtual boundary pulls
+ * in, by the rows left to it (luma 0..3, chroma 0..1) | per luma 4 x 4 block: transpose 0..3 | fixed filter set s (0..15) with class c at ORC_ALF_SET_CLASS + 25 s + c */
+enum { ORC_ALF_CLIP_0, ORC_ALF_CLIP_MAX, ORC_ALF_CLIP_IDX_USED, ORC_ALF_CLIP_IDX_CUT = 6, ORC_ALF_VB_LUMA = 10, ORC_ALF_VB_CHROMA = 14, ORC_ALF_TRANSPOSE = 16, ORC_ALF_SET_CLASS = 20,
+       ORC_ALF_COUNTERS = 420 };
+void     orc_alf_counters(int64_t *out /* [ORC_ALF_COUNTERS] */);
 /* the encoder's SAO statistics (EL/EncSampleAdaptiveOffset.cpp getStatistics, SAOLcuBoundary 0): out [ctu][component][type 0..4][count | diff][32] int64.  PARITY UNPINNED
  * for the region rules (see orc_sao.c) */
 int      orc_sao_statistics(int w, int h, int bit_depth, int tile_cols, int tile_rows, int lf_across_tiles, const int16_t *const org[3], const int16_t *const rec[3], int64_t *out);

@@ -475,6 +475,123 @@ def gen_deblock():
                         forced_meta=np.array(fmeta, np.int32), forced_planes=np.concatenate(fplanes))
 
 
+def _ref_filter_env(W, H, bd, planes, tiles=None):
+    env = R.ref_env_create(W, H, bd)
+    if tiles:
+        R.ref_env_set_tiles.argtypes = [C.c_void_p, C.c_int, C.c_int]; R.ref_env_set_tiles(env, tiles[0], tiles[1])
+    R.ref_env_reset(env)
+    for c in range(3):
+        a = np.ascontiguousarray(planes[c].astype(np.int16)); R.ref_env_set_reco(env, c, P(a), a.shape[1])
+    return env, [np.zeros((H, W), np.int16), np.zeros((H // 2, W // 2), np.int16), np.zeros((H // 2, W // 2), np.int16)]
+
+
+def _save_range(name, meta, deltas, extra=None, parts=1):
+    """a range fixture in `parts` files of whole cases: meta rows and the concatenated int16 differences of each part (and per-case extras)"""
+    n = len(meta); cut = [(i * n) // parts for i in range(parts + 1)]
+    for k in range(parts):
+        f = os.path.join(HERE, name + ("" if k == 0 else "_%d" % (k + 1)) + ".npz")
+        kw = dict(meta=np.array(meta[cut[k]:cut[k + 1]], np.int32), delta=np.concatenate([d for c in deltas[cut[k]:cut[k + 1]] for d in c]))
+        if extra:
+            kw.update({key: np.concatenate(v[cut[k]:cut[k + 1]]) for key, v in extra.items()})
+        np.savez_compressed(f, **kw)
+        print(os.path.basename(f) + ":", cut[k + 1] - cut[k], "cases,", os.path.getsize(f), "bytes")
+        assert os.path.getsize(f) <= 1043003, "larger than the largest fixture there is (lfnst.npz): use more parts"
+
+
+def gen_deblock_range():
+    """The reference's LoopFilter::loopFilterPic on CU tables built by construction (oracle_lib.deblock_quilt: every pair of transform sizes on either side of a vertical, a
+    horizontal and a CTU-top edge) under pictures made to reach every decision of the filter (oracle_lib.deblock_picture), at the ends of the QP range, with slice offsets that
+    clip the table indices, tc = 0 or beta = 0 alone, different Cb / Cr QPs, bit depths 8 / 10 / 12: the fixture keeps the case rows, the chroma QPs the edges were filtered at
+    and filtered - unfiltered as int16.  The oracle's branch counters (equal outputs asserted first) prove the coverage."""
+    import sys
+    sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_lib as O
+    R.ref_env_deblock.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    R.ref_env_set_deblock_offsets.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    W = H = 256
+    meta, deltas, by_bd = [], [], {}
+    O.filter_counters("deblock")
+    for case in O.deblock_range_cases():
+        bd, pat, qp, boff, toff, cbo, cro, forced, seed = case
+        rows, pl = O.deblock_range_inputs(case)
+        tab = np.zeros(64 + 6 * (bd - 8), np.int32)
+        assert R.ref_chroma_qp_table(bd, 3, P(np.array([2, 31, 43], np.int32)), P(np.array([2, 32, 41], np.int32)), P(tab)) == 0
+        qpc = [int(np.clip(tab[qp + 6 * (bd - 8)] + o, 0, 63)) for o in (cbo, cro)]      # CL/LoopFilter.cpp:1338-1339
+        env, outs = _ref_filter_env(W, H, bd, pl)
+        R.ref_env_set_deblock_offsets(env, boff, toff)
+        assert R.ref_env_deblock(env, P(rows), len(rows), qp, cbo, cro, P(outs[0]), P(outs[1]), P(outs[2])) == 0
+        mine = O.deblock_table(pl, rows, bd, qp, qpc, boff, toff)
+        cnt = O.filter_counters("deblock")
+        assert all(np.array_equal(mine[c], outs[c]) for c in range(3)), ("oracle != reference", case)
+        by_bd[bd] = by_bd.get(bd, 0) + cnt
+        changed = [int((outs[c] != pl[c]).sum()) for c in range(3)]
+        if (bd, qp, boff, toff) == (8, 20, -6, 6):
+            assert changed[0] == 0 and changed[1] > 0 and changed[2] > 0, changed           # beta = 0, tc > 0: luma untouched, the unconditional weak chroma filter runs
+        print("deblock range", case, "chroma QPs", qpc, "changed", changed)
+        meta.append(case[:8] + tuple(qpc) + (seed,)); deltas.append([(outs[c] - pl[c]).astype(np.int16).ravel() for c in range(3)])
+    tot = O.check_deblock_range_counters(by_bd)
+    print("deblock range counters", tot)
+    for bd in by_bd:
+        print("  bit depth", bd, dict(zip(O.DB_COUNTERS, by_bd[bd].tolist())))
+    _save_range("deblock_range", meta, deltas, parts=2)
+
+
+def gen_sao_range():
+    """The reference's SampleAdaptiveOffset::SAOProcess at the ends of its inputs (oracle_lib.sao_range_cases / sao_range_params): every coded offset +-max or +-1
+    (max 7 at 8 bit, 31 from 10 bit: getMaxOffsetQVal, CL/SampleAdaptiveOffset.h:72), offset scales 0 / 2 / 4, band positions at the start, the middle and the wrap of the band
+    table, pictures at the ends of the sample range, bit depths 8 / 10 / 12, tiles with and without filtering across them, a picture wider than 1024 samples."""
+    import sys
+    sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_lib as O
+    R.ref_env_sao.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    meta, deltas, tot = [], [], 0
+    O.filter_counters("sao")
+    for case in O.sao_range_cases():
+        W, H, bd, tc, tr, lf, sc, pat, seed = case
+        pl = O.range_picture(W, H, bd, pat); prm = O.sao_range_params(case)
+        env, outs = _ref_filter_env(W, H, bd, pl, (tc, tr))
+        assert R.ref_env_sao(env, P(np.ascontiguousarray(prm)), lf, sc, P(outs[0]), P(outs[1]), P(outs[2])) == 0, case
+        mine = O.sao_picture(pl, W, H, bd, prm, tc, tr, lf, sc)
+        tot = tot + O.filter_counters("sao")
+        assert all(np.array_equal(mine[c], outs[c]) for c in range(3)), ("oracle != reference", case)
+        print("sao range", case, "changed", [int((outs[c] != pl[c]).sum()) for c in range(3)])
+        meta.append(case); deltas.append([(outs[c] - pl[c]).astype(np.int16).ravel() for c in range(3)])
+    O.check_sao_range_counters(tot)
+    print("sao range counters: edge type x class", tot[:20].reshape(4, 5).tolist(), "band k", tot[20:24].tolist(), "wrap, clip 0, clip max, outside picture, other tile", tot[24:29].tolist())
+    _save_range("sao_range", meta, deltas)
+
+
+def gen_alf_range():
+    """The reference's AdaptiveLoopFilter::ALFProcess at the ends of its inputs (oracle_lib.alf_range_cases / alf_range_params): coefficients of +-127 (the range the reference's
+    encoder keeps a parameter set in, EL/EncAdaptiveLoopFilter.cpp:2282-2283), linear and non-linear filters with every clipping index on every tap, pictures at the ends of the
+    sample range, bit depths 8 / 10 / 12, partial CTUs shorter than the virtual boundary's distance, and a picture in which every fixed filter set meets every class."""
+    import sys
+    sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_lib as O
+    R.ref_env_alf.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    meta, deltas, classes, tot = [], [], [], 0
+    O.filter_counters("alf")
+    for case in O.alf_range_cases():
+        W, H, bd, pic, kind, seed = case
+        pl = O.alf_range_picture(case); prm = O.alf_range_params(case)
+        env, outs = _ref_filter_env(W, H, bd, pl)
+        cls = np.zeros((H // 4, W // 4), np.uint8)
+        aps = np.ascontiguousarray(prm["aps"], np.int32); la = np.ascontiguousarray(prm["luma_aps"], np.int32); ctu = np.ascontiguousarray(prm["ctu"], np.int32)
+        assert R.ref_env_alf(env, bd, len(aps), P(aps), len(la), P(la), prm["chroma_aps"], P(ctu), P(outs[0]), P(outs[1]), P(outs[2]), P(cls)) == 0, case
+        mine, mcls = O.alf_picture(pl, W, H, bd, prm, want_classes=True)
+        tot = tot + O.filter_counters("alf")
+        assert np.array_equal(mcls, cls) and all(np.array_equal(mine[c], outs[c]) for c in range(3)), ("oracle != reference", case, [int((mine[c] != outs[c]).sum()) for c in range(3)])
+        if pic == 6:
+            one = cls[:32, :32]
+            assert len(np.unique(one & 31)) == 25 and len(np.unique(one >> 5)) == 4, "the patch must show every class and every transpose"
+        print("alf range", case, "changed", [int((outs[c] != pl[c]).sum()) for c in range(3)], "classes", len(np.unique(cls & 31)))
+        meta.append(case); deltas.append([(outs[c] - pl[c]).astype(np.int16).ravel() for c in range(3)]); classes.append(cls.ravel())
+    O.check_alf_range_counters(tot)
+    print("alf range counters: clip 0 / max", tot[0:2].tolist(), "clip index used", tot[2:6].tolist(), "cut", tot[6:10].tolist(), "virtual boundary luma", tot[10:14].tolist(), "chroma", tot[14:16].tolist(),
+          "transposes", tot[16:20].tolist(), "(fixed set, class) pairs hit", int((tot[20:420] > 0).sum()), "of 400, fewest blocks", int(tot[20:420].min()))
+    _save_range("alf_range", meta, deltas, dict(classes=classes))
+
+
 def gen_sao():
     """The reference's SampleAdaptiveOffset::SAOProcess with seeded per-CTU parameters (all five types, merges, every tile-border case) on seeded pictures: the fixture keeps
     the filtered planes; the parameters and the pictures are regenerated by the tests (oracle_lib.sao_params / SAO_CASES)."""
@@ -1568,6 +1685,8 @@ if __name__ == "__main__":
         gen_alf(); sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "deblock":
         gen_deblock(); sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] in ("deblock_range", "sao_range", "alf_range"):
+        globals()["gen_" + sys.argv[1]](); sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "chroma_qp":
         gen_chroma_qp(); sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "bitstream_mip":
@@ -1605,5 +1724,5 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "cclm":
         gen_cclm(); sys.exit(0)      # added later: leaves the earlier fixtures (and the shared rng stream they used) untouched
     gen_transforms(); gen_dist(); gen_cabac(); gen_scan(); gen_intra(); gen_partition(); gen_trquant(); gen_bitstream(); gen_cclm(); gen_bitstream_cclm(); gen_trquant_mts(); gen_bitstream_mts(); gen_bitstream_mip(); gen_chroma_qp(); gen_deblock(); gen_mip(); gen_depquant(); gen_bitstream_dq(); gen_lfnst(); gen_bitstream_lfnst(); gen_bitstream_jccr(); gen_ict(); gen_decision_helpers(); gen_ts(); gen_bitstream_ts(); gen_isp(); gen_bitstream_isp(); gen_lmcs(); gen_bitstream_wpp(); gen_lmcs_analysis(); gen_sao(); gen_alf(); gen_trquant_range()
-    gen_intra_shapes(); gen_cclm_shapes(); gen_mip_range(); gen_dist_range()      # seeds of their own: the order does not matter
+    gen_intra_shapes(); gen_cclm_shapes(); gen_mip_range(); gen_dist_range(); gen_deblock_range(); gen_sao_range(); gen_alf_range()      # seeds of their own: the order does not matter
     print("done")

@@ -523,6 +523,29 @@ def test_deblocking_filter(case):
     enc.close()
 
 
+@pytest.mark.parametrize("offsets", [(-3, 4), (6, -6)])
+def test_deblocking_filter_with_slice_offsets(offsets):
+    """vvcx_deblock_bound_frames with non-zero beta_offset_div2 / tc_offset_div2 against the oracle's deblocking with the same offsets (pinned to the reference with offsets
+    by tests/golden/deblock_range*.npz) behind the same search: 128 x 128, QP 32"""
+    import torch
+    W, H, qp = 128, 128, 32
+    sp = pkg.slice_params(qp)
+    planes = pkg.synth_frame(W, H, 0, 8, 7, chroma_texture=0.5)
+    enc = pkg.VvcxEncoder(W, H, 8, tools=MTS)
+    enc.set_slice(sp["qp"], sp["qp_c"], sp["lam"], sp["dist_weight"])
+    org = [torch.from_numpy(np.ascontiguousarray(p)).cuda() for p in planes]
+    rec = [torch.zeros_like(t) for t in org]
+    enc.bind_frames([([t.data_ptr() for t in org], [t.data_ptr() for t in rec], [t.shape[1] for t in org])])
+    enc.compress_bound_frames()
+    enc.deblock_bound_frames(*offsets)
+    plain = O.compress_frame(planes, W, H, sp, tools=MTS, deblock=True)[2]
+    oreco = O.compress_frame(planes, W, H, sp, tools=MTS, deblock=True, deblock_offsets=offsets)[2]
+    assert any((oreco[c] != plain[c]).any() for c in range(3))                 # the offsets matter on this picture
+    for c in range(3):
+        assert np.array_equal(rec[c].cpu().numpy(), oreco[c]), (offsets, c)
+    enc.close()
+
+
 def test_sample_adaptive_offset_filter_on_the_gpu():
     """The SAO kernels (csrc/vvcx_sao.hip) on the GPU: vvcx_sao_picture against the reference's planes (tests/golden/sao.npz), and vvcx_sao_bound_frames behind a search
     and the deblocking filter against the oracle's filter on the same reconstruction (four pictures of 3 x 2 tiles, without filtering across tile borders)."""

@@ -513,6 +513,54 @@ def test_emulated_leaf_operators_match_reference_at_shapes_and_range_edges(emu_s
         assert _dist_range(emu_so, bd, ((2, 2), (2, 16), (4, 4), (8, 4), (4, 8), (8, 8), (16, 8), (8, 16), (64, 16))) == 9 * 9
 
 
+def _deblock_range(lib, want):
+    import oracle_lib as O
+    return O.check_deblock_range(lambda pl, rows, bd, qp, qpc, boff, toff: pkg.vvcx.deblock_cu_table(pl, rows, bd, qp, qpc, boff, toff, lib_path=lib), want)
+
+
+def _sao_range(lib, want):
+    import oracle_lib as O
+    return O.check_sao_range(lambda pl, bd, prm, tc, tr, lf, sc: pkg.vvcx.sao_picture(pl, bd, prm, tc, tr, lf, sc, lib_path=lib), want)
+
+
+def _alf_range(lib, want):
+    import oracle_lib as O
+    return O.check_alf_range(lambda pl, bd, prm: pkg.vvcx.alf_picture(pl, bd, prm, want_classes=True, lib_path=lib), want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bd,n", [(8, 47), (10, 4), (12, 4)])
+def test_gpu_deblocking_matches_reference_at_qp_limits_offsets_and_range_edges(bd, n):
+    """vvcx_deblock_cu_table against the REFERENCE's filtered planes of tests/golden/deblock_range*.npz: QP 0..63, offsets that clip the table indices, tc = 0 / beta = 0 alone,
+    Cb != Cr, every pair of transform sizes on every kind of edge, forced ISP splits"""
+    assert _deblock_range(None, lambda m: m[0] == bd) == n
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bd,n", [(8, 13), (10, 14), (12, 13)])
+def test_gpu_sample_adaptive_offset_matches_reference_at_offset_limits_and_range_edges(bd, n):
+    """vvcx_sao_picture against the REFERENCE's planes of tests/golden/sao_range.npz: offsets of +-max and +-1, offset scales 0 / 2 / 4, the band wrap, both clips, tiles, 1032 samples wide"""
+    assert _sao_range(None, lambda m: m[2] == bd) == n
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bd,n", [(8, 10), (10, 12), (12, 10)])
+def test_gpu_adaptive_loop_filter_matches_reference_at_coefficient_limits_and_range_edges(bd, n):
+    """vvcx_alf_picture (planes and block classes) against the REFERENCE's of tests/golden/alf_range.npz: coefficients of +-127, every clipping index on every tap, partial CTUs,
+    every (fixed filter set, class) pair"""
+    assert _alf_range(None, lambda m: m[2] == bd) == n
+
+
+def test_emulated_loop_filters_match_reference_at_limits_and_range_edges(emu_so):
+    """the cases of the three loop-filter range fixtures that the CPU emulation of the kernel sources can afford (oracle_lib.DEBLOCK_EMU / SAO_EMU / ALF_EMU): deblocking with
+    both table indices clipped at either end, tc = 0 alone, beta = 0 alone, Cb != Cr, 10 and 12 bit, forced ISP; SAO wider than 1024 samples and with the largest offsets on
+    pictures at the ends of the range; ALF with +-127 coefficients on the small pictures and with every fixed filter set on every class"""
+    import oracle_lib as O
+    assert _deblock_range(emu_so, O.DEBLOCK_EMU) == 10
+    assert _sao_range(emu_so, O.SAO_EMU) == 13
+    assert _alf_range(emu_so, O.ALF_EMU) == 13
+
+
 @pytest.mark.gpu
 def test_mip_prediction():
     """Device MIP prediction (vvcx_mip.hip: one wave per block, closed-form up-sampling) against MatrixIntraPrediction of the reference:

@@ -1006,3 +1006,61 @@ def test_distortion_at_the_ends_of_the_range():
         assert L.orc_sse(P(a), w, P(b), w, w, h) == sse, ("sse", w, h, bd, k)
         n += 1
     assert n == 648
+
+
+def test_deblocking_filter_at_qp_limits_offsets_and_range_edges_against_the_reference():
+    """tests/golden/deblock_range*.npz (make_golden.py deblock_range): orc_deblock_table_offsets on the regenerated quilt tables and pictures equals, sample by sample, what the
+    reference's LoopFilter made of them at QP 0..63, with slice offsets that clip the table indices, with tc = 0 or beta = 0 alone, with different Cb / Cr QPs, at 8 / 10 / 12
+    bit, on forced ISP splits.  The branch counters of the oracle - which therefore describe the reference's run as well - show every decision of the filter taken, the long
+    and short filters at each bit depth."""
+    by_bd = {}
+    O.filter_counters("deblock")
+    def run(pl, rows, bd, qp, qpc, boff, toff):
+        out = O.deblock_table(pl, rows, bd, qp, qpc, boff, toff)
+        by_bd[bd] = by_bd.get(bd, 0) + O.filter_counters("deblock")
+        return out
+    assert O.check_deblock_range(run) == len(O.deblock_range_cases()) == 55
+    O.check_deblock_range_counters(by_bd)
+    metas = np.concatenate([g["meta"] for g in O.range_fixture("deblock_range")])
+    assert [tuple(m[:8]) + (m[10],) for m in metas.tolist()] == O.deblock_range_cases()
+    assert (metas[:, 8] != metas[:, 9]).any() and (metas[:, 8] == 63).any()          # Cb / Cr filtered at different QPs, one of them clipped at 63
+
+
+def test_sample_adaptive_offset_at_offset_limits_and_range_edges_against_the_reference():
+    """tests/golden/sao_range.npz (make_golden.py sao_range): orc_sao_picture equals the reference's SAOProcess with every coded offset at +-max or +-1, offset scales 0 / 2 / 4,
+    band positions 0, 15 and 28..31, pictures at the ends of the sample range, 8 / 10 / 12 bit, tiles, a picture wider than 1024 samples; the counters show every class of
+    every edge type, every band offset, the band wrap, both clips and both kinds of unavailable neighbour."""
+    O.filter_counters("sao")
+    assert O.check_sao_range(lambda pl, bd, prm, tc, tr, lf, sc: O.sao_picture(pl, pl[0].shape[1], pl[0].shape[0], bd, prm, tc, tr, lf, sc)) == len(O.sao_range_cases()) == 40
+    O.check_sao_range_counters(O.filter_counters("sao"))
+    for bd in (8, 10, 12):
+        prm = np.concatenate([O.sao_range_params(c).reshape(-1, 7) for c in O.sao_range_cases() if c[2] == bd])
+        new = prm[prm[:, 0] == 1]
+        assert {int(v) for v in new[:, 3:].ravel()} == {O.sao_max_offset(bd), -O.sao_max_offset(bd), 1, -1} and {int(v) for v in new[new[:, 1] == 4][:, 2]} == {0, 15, 28, 29, 30, 31}
+        assert {int(v) for v in new[:, 1]} == {0, 1, 2, 3, 4} and {tuple(v) for v in prm[prm[:, 0] == 2][:, :2].tolist()} == {(2, 0), (2, 1)}
+    assert [O.sao_max_offset(bd) for bd in (8, 10, 12)] == [7, 31, 31]
+
+
+def test_adaptive_loop_filter_at_coefficient_limits_and_range_edges_against_the_reference():
+    """tests/golden/alf_range.npz (make_golden.py alf_range): orc_alf_picture equals the reference's ALFProcess (planes and block classes) with coefficients of +-127, linear and
+    non-linear filters with every clipping index on every tap, pictures at the ends of the sample range, 8 / 10 / 12 bit, partial CTUs, and every fixed filter set on a patch
+    that shows every class; the counters show both clips, every clipping index used and (1..3) cutting, every distance to a virtual boundary, the four transposes and all
+    16 x 25 (fixed set, class) pairs."""
+    O.filter_counters("alf")
+    assert O.check_alf_range(lambda pl, bd, prm: O.alf_picture(pl, pl[0].shape[1], pl[0].shape[0], bd, prm, want_classes=True)) == len(O.alf_range_cases()) == 32
+    O.check_alf_range_counters(O.filter_counters("alf"))
+    prm = O.alf_range_params(O.alf_range_cases()[0])["aps"]
+    assert np.abs(prm[:, 27:327]).max() == np.abs(prm[:, 636:684]).max() == O.ALF_MAX_COEFF == 127
+    assert all(set(prm[0, 327:627].reshape(25, 12)[:, k]) == {0, 1, 2, 3} for k in range(12)) and all(set(prm[0, 684:732].reshape(8, 6)[:, k]) == {0, 1, 2, 3} for k in range(6))
+
+
+def test_deblock_quilt_covers_every_pair_of_transform_sizes():
+    """oracle_lib.deblock_quilt asserts its own coverage from the table; here the table is also a legal one: both trees tile the picture with CUs of the allowed sizes"""
+    for isp in (0.12, 1):
+        rows = O.deblock_quilt(256, 256, O.DB_QUILT_SEED, isp)
+        for ch in (0, 1):
+            t = rows[rows[:, 0] == ch]
+            assert int((t[:, 3] * t[:, 4]).sum()) == 256 * 256 and set(t[:, 3].tolist()) | set(t[:, 4].tolist()) == ({4, 8, 16, 32, 64} if ch == 0 else {8, 16, 32, 64})
+            assert ((t[:, 1] >> 7) == ((t[:, 1] + t[:, 3] - 1) >> 7)).all() and ((t[:, 2] >> 7) == ((t[:, 2] + t[:, 4] - 1) >> 7)).all()      # no CU straddles a CTU
+        assert (rows[rows[:, 0] == 1][:, 5] == 0).all() and ((rows[:, 5] > 0).sum() > 40)
+
