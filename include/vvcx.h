@@ -212,7 +212,7 @@ float vvcx_last_deblock_ms(const vvcx_handle *h);
  * 2 merge; type: for a new CTU 0..3 = edge class 0 / 90 / 135 / 45 degrees, 4 = band offset, for a merge 0 = from the CTU to the left, 1 = from the CTU above (which must be
  * in the same tile); band = band position (0..31); offset[4] = the four coded offsets (edge: full valley, half valley, half peak, full peak; band: the four bands from the
  * band position), multiplied by 2^log2_offset_scale.  lf_across_tiles = pps loop_filter_across_bricks_enabled_flag.  The parameter DECISION (EncSampleAdaptiveOffset) is
- * not part of the library: the caller's encoder keeps it.  In the reference's order this follows vvcx_deblock_bound_frames. */
+ * vvcx_sao_statistics_bound_frames + vvcx_sao_decide below.  In the reference's order this follows vvcx_deblock_bound_frames. */
 typedef struct vvcx_sao_param { int8_t mode, type, band, offset[4]; } vvcx_sao_param;
 int   vvcx_sao_bound_frames(vvcx_handle *h, const vvcx_sao_param *prm, int lf_across_tiles, int log2_offset_scale, void *hip_stream);
 float vvcx_last_sao_ms(const vvcx_handle *h);
@@ -244,7 +244,7 @@ int   vvcx_sao_picture(int pic_w, int pic_h, int bit_depth, int tile_cols, int t
  * ctus[frame][ctu raster address]: enable flags Y / Cb / Cr (≙ Picture::getAlfCtuEnableFlag), luma filter set (getAlfCtbFilterIndex), chroma alternatives
  * (getAlfCtuAlternativeData).  Class derivation (deriveClassificationBlk 792-1002), the 7 x 7 / 5 x 5 diamond filters with clipping (filterBlk 1005-1296) and the virtual
  * boundary above every lower CTU border are the reference's; tiles are not looked at (its ALF of this version does not either).  The parameter DECISION
- * (EncAdaptiveLoopFilter) is not part of the library.  In the reference's order this follows vvcx_sao_bound_frames. */
+ * (EncAdaptiveLoopFilter) is vvcx_alf_statistics_bound_frames + vvcx_alf_decide below (linear filters).  In the reference's order this follows vvcx_sao_bound_frames. */
 typedef struct vvcx_alf_aps {
   int32_t num_luma_filters; uint8_t class_to_filter[25]; uint8_t nonlinear_luma; int16_t luma_coeff[25][12]; uint8_t luma_clip_idx[25][12];
   int32_t num_chroma_alt; uint8_t nonlinear_chroma[8]; int16_t chroma_coeff[8][6]; uint8_t chroma_clip_idx[8][6];
@@ -257,6 +257,43 @@ float vvcx_last_alf_ms(const vvcx_handle *h);
  * every luma 4 x 4 block of the CTUs with luma enabled (255 elsewhere), (pic_w / 4) per row */
 int   vvcx_alf_picture(int pic_w, int pic_h, int bit_depth, const vvcx_alf_aps *aps, int n_aps, const vvcx_alf_slice *slice, const vvcx_alf_ctu *ctus,
                        uint16_t *y, uint16_t *cb, uint16_t *cr, uint8_t *classes, int device);
+/* ---- the encoder side of ALF (EL/EncAdaptiveLoopFilter.cpp).  Call order of the loop-filter stage on bound pictures:
+ *   vvcx_deblock_bound_frames -> vvcx_sao_statistics_bound_frames -> vvcx_sao_decide -> vvcx_sao_bound_frames
+ *   -> vvcx_alf_statistics_bound_frames -> vvcx_alf_decide -> vvcx_alf_bound_frames
+ *
+ * ≙ EncAdaptiveLoopFilter::deriveStatsForFiltering (EL/EncAdaptiveLoopFilter.cpp:2650-2745; getBlkStats 2746-2843, calcCovariance 2844-2965, m_alfWSSD off): the content of
+ * AlfCovariance per CTU and class, gathered on the device from the original and the picture the ALF filter would read (after deblocking and SAO).  Per sample s and
+ * clipping bin b < n_bins (n_bins = 1: bin 0 only, enough for linear filters; or 4):  v[k][b] = clip(-C_b, C_b, r0 - cur) + clip(-C_b, C_b, r1 - cur)  for the tap pairs
+ * k = 0..11 (luma) / 0..5 (chroma), k being the coefficient index of vvcx_alf_aps.luma_coeff / chroma_coeff (luma: after the block's transpose index has been applied),
+ * v[12 / 6][b] = cur, C_b = the clipping value of index b (C_0 = 1 << bit_depth: no clipping), d = org - cur; vertical tap distances shorten at the virtual boundary and
+ * picture borders repeat the edge sample exactly as in the filter.  Per (CTU, class; chroma: per CTU and component) the exact int64 sums
+ *   E[b0][b1][k][l] = sum v[k][b0] v[l][b1] (the full array: E[b0][b1][k][l] == E[b1][b0][l][k]),  y[b][k] = sum v[k][b] d,  pixAcc = sum d d
+ * in the order E, y, pixAcc:  luma[frame][ctu][25][nb*nb*169 + nb*13 + 1],  chroma[frame][ctu][2][nb*nb*49 + nb*7 + 1]  (host memory; 4 bins are about 550 KB per CTU,
+ * hence the frame range of the bound form).  Every block of the picture is classified, whatever flags its CTU gets later; class and transpose index are the filter's.
+ * The host-plane form needs no handle (like vvcx_alf_picture): org / rec = uint16 planes, stride = plane width; chroma may be NULL (luma only). */
+int   vvcx_alf_statistics_picture(int pic_w, int pic_h, int bit_depth, int n_bins, const uint16_t *const org[3], const uint16_t *const rec[3],
+                                  int64_t *luma, int64_t *chroma, int device);
+/* the same on the bound pictures frame_first .. frame_first + n - 1 (every CTU coded): after vvcx_sao_bound_frames (or vvcx_deblock_bound_frames when SAO is not used),
+ * before vvcx_alf_bound_frames.  VVCX_ERR_UNSUPPORTED for an LMCS slice (the handle keeps the mapped original only).  chroma may be NULL; a handle without chroma fills it
+ * with zeros. */
+int   vvcx_alf_statistics_bound_frames(vvcx_handle *h, int frame_first, int n, int n_bins, int64_t *luma, int64_t *chroma, void *hip_stream);
+float vvcx_last_alf_stats_ms(const vvcx_handle *h);
+/* ≙ EncAdaptiveLoopFilter::ALFProcess (EL/EncAdaptiveLoopFilter.cpp:661; mergeClasses 2344, deriveFilterCoeffs 2158, deriveCoeffQuant 2279, deriveCtbAlfEnableFlags 834)
+ * for ONE picture from its statistics (the [ctu][..] block of that picture, n_bins as gathered; bin 0 is read), LINEAR filters only: nonlinear_luma = 0, clip indices 0.
+ * Host code, needs no handle.  Fills one parameter set (aps[0]), the slice (n_luma_aps = 1, luma_aps = {0}, chroma_aps = 0 or -1) and ctus[ctu] (set = 16).
+ * Luma: the frame statistics are the sum over the enabled CTUs (all at first); the 25 classes are merged greedily down to 1 filter (always the two groups whose merge
+ * raises the least-squares error least) and the filter count <= max_luma_filters with the least distortion + lambda[0] * bits is kept; per group the coefficients are the
+ * Cholesky solution in double (a multiple of the mean diagonal is added while the matrix is singular), rounded to 7 fractional bits in [-128, 127] and refined by single
+ * steps of one coefficient while the predicted error falls - never worse than plain rounding, never worse than the zero filter.  A CTU is enabled where its own statistics
+ * predict  distortion with the filter + lambda * bits < unfiltered distortion; then the filters are derived once more from the enabled CTUs.  Chroma (chroma != 0): one
+ * alternative (6 coefficients) from Cb + Cr, flags per component; chroma_aps = -1 when no CTU of either component gains.
+ * Bits (this project's own count of the syntax, not the reference's estimator): parameter set luma = 1 (clip flag) + ue(filters - 1) + 25 * ceil(log2 filters) when there
+ * are several + per coefficient ue(|c|) + 1 sign bit when c != 0; chroma = 1 + ue(0) + the coefficients; an enabled luma CTU costs one bin more than a disabled one
+ * (alf_use_aps_flag), a chroma CTU's flag costs the same either way; a component whose gain does not pay for its parameter-set bits stays unfiltered.
+ * Out of scope: the clip-index search for nonlinear filters (a caller's encoder can run it from the 4-bin statistics), the fixed filter sets as candidates, several chroma
+ * alternatives, parameter-set reuse across pictures.  Parity with the reference's RD choice is unpinned (the unit does not compile in this environment). */
+int   vvcx_alf_decide(int pic_w, int pic_h, int bit_depth, int chroma, int n_bins, const int64_t *luma, const int64_t *chroma_stats,
+                      const double lambda[3], int max_luma_filters, vvcx_alf_aps *aps, vvcx_alf_slice *slice, vvcx_alf_ctu *ctus);
 /* ≙ LoopFilter::loopFilterPic on a picture the caller describes itself (the way the reference's LoopFilter sees a CodingStructure: cs.cus + cs.tus + the reconstruction buffer):
  * rows = n_rows x {channel type (0 luma tree, 1 chroma tree), x, y, w, h in luma samples, cu.ispMode (0, 1 = horizontal, 2 = vertical split; luma rows only)} covering both
  * trees of the whole 4:2:0 picture, every CU intra at the slice QP (qp_cb / qp_cr = mapped chroma QPs); y / cb / cr = host planes of 16-bit samples, stride = plane width,

@@ -12,6 +12,7 @@
 #include <stdint.h>
 #include "vvcx_dev.h"
 #include "vvcx_alf_tables.h"
+#include "vvcx_alf_dev.h"       // the class derivation, the transpose orders, the reach of the taps at the virtual boundary
 
 #define ALF_TW 64
 #define ALF_TH 16
@@ -19,15 +20,6 @@
 #define ALF_PAD 4                        // the LDS tile starts four samples left of the tile: whole aligned groups of four samples are staged
 #define ALF_LW (ALF_TW + 2 * ALF_PAD)
 #define ALF_LH (ALF_TH + 2 * ALF_HALO)
-
-__device__ static const uint8_t ALF_PERM7[4][12] = { { 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11 }, { 9, 4, 10, 8, 1, 5, 11, 7, 3, 0, 2, 6 }, { 0, 3, 2, 1, 8, 7, 6, 5, 4, 9, 10, 11 }, { 9, 8, 10, 4, 3, 7, 11, 5, 1, 0, 2, 6 } };
-__device__ static const uint8_t ALF_TH_TAB[16] = { 0, 1, 2, 2, 2, 2, 2, 3, 3, 3, 3, 3, 3, 3, 3, 4 };
-__device__ static const uint8_t ALF_TRANSPOSE[8] = { 0, 1, 0, 2, 2, 3, 1, 3 };
-
-__device__ inline int alf_clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
-__device__ inline int alf_min(int a, int b) { return a < b ? a : b; }
-__device__ inline int alf_abs(int v) { return v < 0 ? -v : v; }
-__device__ inline int alf_clip2(int clip, int ref, int a, int b) { return alf_clampi(a - ref, -clip, clip) + alf_clampi(b - ref, -clip, clip); }
 
 // a workgroup copies a strip of 4 rows x 1024 samples: four consecutive samples per lane and row (one word of 8-bit samples, two of 16-bit ones, when both sides are aligned)
 template <typename T>
@@ -72,45 +64,14 @@ __device__ void alf_filter(const VxAlfParams &p)
       else { const Quad q = *(const Quad *) (row + gx); d[0] = (int16_t) q.v[0]; d[1] = (int16_t) q.v[1]; d[2] = (int16_t) q.v[2]; d[3] = (int16_t) q.v[3]; }
     }
   }
-  // the virtual boundary of this CTU row; in the last one the reference passes the LUMA height for every component (ALFProcess 296, 313): only a picture of at most 128
-  // rows reaches it
-  const int vbPos = ctuY == p.ctus_h - 1 ? p.pic_h : ctuS - (c ? 2 : 4);
+  const int vbPos = alf_vb_pos(ctuY, p.ctus_h, p.pic_h, ctuS, c);      // the virtual boundary of this CTU row
   __syncthreads();
 #define TL(x_, y_) ((int) tile[(y_) - ty0 + ALF_HALO][(x_) - tx0 + ALF_PAD])
   if (c == 0) {
-    // ---- classes: lane (block, r) takes the window's row pair r of its block
-    const int b = tid >> 2, r = tid & 3, X = tx0 + ((b & 15) << 2), Y = ty0 + ((b >> 4) << 2), yIn = Y & (ctuS - 1);
-    int sV = 0, sH = 0, sD0 = 0, sD1 = 0;
-    const bool skip = (yIn == vbPos - 4 && r == 3) || (yIn == vbPos && r == 0);      // the window does not cross the boundary
-    if (!skip) {
-      const int y1 = Y - 2 + 2 * r, y2 = y1 + 1;
-      int y0 = y1 - 1, y3 = y2 + 1;
-      if (y1 > 0 && (y1 & (ctuS - 1)) == vbPos - 2) y3 = y2; else if (y1 > 0 && (y1 & (ctuS - 1)) == vbPos) y0 = y1;
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const int x = X - 2 + 2 * k;
-        const int a = TL(x, y1) << 1, bb = TL(x + 1, y2) << 1;
-        sV += alf_abs(a - TL(x, y0) - TL(x, y2)) + alf_abs(bb - TL(x + 1, y1) - TL(x + 1, y3));
-        sH += alf_abs(a - TL(x + 1, y1) - TL(x - 1, y1)) + alf_abs(bb - TL(x + 2, y2) - TL(x, y2));
-        sD0 += alf_abs(a - TL(x - 1, y0) - TL(x + 1, y2)) + alf_abs(bb - TL(x, y1) - TL(x + 2, y3));
-        sD1 += alf_abs(a - TL(x - 1, y2) - TL(x + 1, y0)) + alf_abs(bb - TL(x, y3) - TL(x + 2, y1));
-      }
-    }
-    sV += __shfl_xor(sV, 1); sH += __shfl_xor(sH, 1); sD0 += __shfl_xor(sD0, 1); sD1 += __shfl_xor(sD1, 1);
-    sV += __shfl_xor(sV, 2); sH += __shfl_xor(sH, 2); sD0 += __shfl_xor(sD0, 2); sD1 += __shfl_xor(sD1, 2);
+    // ---- classes: lane (block, r) takes the window's row pair r of its block (vvcx_alf_dev.h)
+    const int b = tid >> 2, r = tid & 3, X = tx0 + ((b & 15) << 2), Y = ty0 + ((b >> 4) << 2);
+    const int v = alf_class_of_block([&](int x, int y) { return TL(x, y); }, X, Y, r, ctuS, vbPos, p.bit_depth);
     if (r == 0) {
-      const int scaled = (yIn == vbPos - 4 || yIn == vbPos) ? 96 : 64;
-      int cls = ALF_TH_TAB[alf_clampi(((sV + sH) * scaled) >> (p.bit_depth + 4), 0, 15)];
-      int hv1, hv0, d1, d0, dirHV, dirD, hvd1, hvd0, mainDir, secDir;
-      if (sV > sH) { hv1 = sV; hv0 = sH; dirHV = 1; } else { hv1 = sH; hv0 = sV; dirHV = 3; }
-      if (sD0 > sD1) { d1 = sD0; d0 = sD1; dirD = 0; } else { d1 = sD1; d0 = sD0; dirD = 2; }
-      if ((uint32_t) d1 * (uint32_t) hv0 > (uint32_t) hv1 * (uint32_t) d0) { hvd1 = d1; hvd0 = d0; mainDir = dirD; secDir = dirHV; }
-      else { hvd1 = hv1; hvd0 = hv0; mainDir = dirHV; secDir = dirD; }
-      int strength = 0;
-      if (hvd1 > 2 * hvd0) strength = 1;
-      if (hvd1 * 2 > 9 * hvd0) strength = 2;
-      if (strength) cls += (((mainDir & 1) << 1) + strength) * 5;
-      const int v = cls | (ALF_TRANSPOSE[mainDir * 2 + (secDir >> 1)] << 5);
       cls_of[b] = (uint8_t) v;
       if (p.classes && X < pw && Y < ph) p.classes[(size_t) f * (p.pic_w >> 2) * (p.pic_h >> 2) + (size_t) (Y >> 2) * (p.pic_w >> 2) + (X >> 2)] = (uint8_t) v;
     }
@@ -119,10 +80,7 @@ __device__ void alf_filter(const VxAlfParams &p)
   // ---- the filter: lane -> (row of the tile, group of four samples)
   const int row = tid >> 4, grp = tid & 15, X = tx0 + (grp << 2), Y = ty0 + row;
   if (X >= pw || Y >= ph) return;
-  const int yVb = Y & (ctuS - 1), reach = c ? 2 : 4;
-  int d1 = 1, d2 = 2, d3 = 3;
-  if (yVb < vbPos && yVb >= vbPos - reach) { const int room = vbPos - 1 - yVb; d1 = alf_min(d1, room); d2 = alf_min(d2, room); d3 = alf_min(d3, room); }
-  else if (yVb >= vbPos && yVb <= vbPos + reach - 1) { const int room = yVb - vbPos; d1 = alf_min(d1, room); d2 = alf_min(d2, room); d3 = alf_min(d3, room); }
+  const int room = alf_vb_room(Y & (ctuS - 1), vbPos, c), d1 = alf_min(1, room), d2 = alf_min(2, room), d3 = alf_min(3, room);
   const VxAlfFrame &tb = p.tabs[f];
   const int maxv = (1 << p.bit_depth) - 1;
   int out[4];

@@ -39,6 +39,10 @@ extern "C" __global__ void vvcx_alf_copy_kernel_u8(VxAlfParams p);
 extern "C" __global__ void vvcx_alf_copy_kernel_u16(VxAlfParams p);
 extern "C" __global__ void vvcx_alf_kernel_u8(VxAlfParams p);
 extern "C" __global__ void vvcx_alf_kernel_u16(VxAlfParams p);
+extern "C" __global__ void vvcx_alf_stats_b1_kernel_u8(VxAlfStatParams p);
+extern "C" __global__ void vvcx_alf_stats_b4_kernel_u8(VxAlfStatParams p);
+extern "C" __global__ void vvcx_alf_stats_b1_kernel_u16(VxAlfStatParams p);
+extern "C" __global__ void vvcx_alf_stats_b4_kernel_u16(VxAlfStatParams p);
 extern "C" __global__ void vvcx_deblock_edges_kernel(VxDeblockParams p);
 extern "C" __global__ void vvcx_deblock_kernel_u8(VxDeblockParams p);
 extern "C" __global__ void vvcx_deblock_kernel_u16(VxDeblockParams p);
@@ -98,6 +102,7 @@ struct vvcx_handle {
   DevBuf<uint8_t> db_edges_d;      // vvcx_deblock_bound_frames: one edge byte per unit, map and direction
   DevBuf<long long> sao_stat_d; float last_sao_stats_ms;      // vvcx_sao_statistics_bound_frames
   DevBuf<VxAlfFrame> alf_tab_d; DevBuf<VxAlfCtu> alf_ctu_d; float last_alf_ms;      // vvcx_alf_bound_frames: per-frame tables and per-CTU choices (the picture copy is the SAO one)
+  DevBuf<long long> alf_stat_luma_d, alf_stat_chroma_d; float last_alf_stats_ms;      // vvcx_alf_statistics_bound_frames
   // a submitted, not yet collected launch (vvcx_submit_ctus .. vvcx_wait_ctus): staging the async copies read from / write to stays alive here
   bool pending; hipStream_t pend_stream; int pend_n; VxCtuRes *pend_res; int pend_cap;
   std::vector<VxStreamDesc> pend_sd; std::vector<int32_t> pend_task_ctu; std::vector<int> pend_src, pend_next; VxDqConst pend_dq[17 * 96];
@@ -1266,6 +1271,256 @@ extern "C" int vvcx_alf_picture(int pic_w, int pic_h, int bit_depth, const vvcx_
   return VVCX_OK;
 }
 extern "C" float vvcx_last_alf_ms(const vvcx_handle *h) { return h ? h->last_alf_ms : 0.f; }
+
+// ---- the encoder side of ALF.  The statistics (≙ EncAdaptiveLoopFilter::deriveStatsForFiltering, EL/EncAdaptiveLoopFilter.cpp:2650-2745 -> getBlkStats / calcCovariance)
+// are gathered on the device (vvcx_alf_stats.hip): per (CTU, class) E | y | pixAcc as int64, nc = 13 luma / 7 chroma coefficients, nb clipping bins.
+static size_t alf_stat_size(int nb, int nc) { return (size_t) nb * nb * nc * nc + (size_t) nb * nc + 1; }
+static void alf_stats_launch(VxAlfStatParams &p, int n_frames, int nb, size_t bps, hipStream_t stream)
+{
+  for (int b = 0; b < 4; b++) { p.clip[0][b] = alf_clip_value(0, p.bit_depth, b); p.clip[1][b] = alf_clip_value(1, p.bit_depth, b); }
+  const dim3 grid((unsigned) (p.ctus_w * p.ctus_h), p.chroma ? 3u : 1u, (unsigned) n_frames);      // one workgroup owns one (CTU, component, frame)
+  if (bps == 1) { if (nb == 1) hipLaunchKernelGGL(vvcx_alf_stats_b1_kernel_u8, grid, dim3(256), 0, stream, p); else hipLaunchKernelGGL(vvcx_alf_stats_b4_kernel_u8, grid, dim3(256), 0, stream, p); }
+  else { if (nb == 1) hipLaunchKernelGGL(vvcx_alf_stats_b1_kernel_u16, grid, dim3(256), 0, stream, p); else hipLaunchKernelGGL(vvcx_alf_stats_b4_kernel_u16, grid, dim3(256), 0, stream, p); }
+}
+extern "C" int vvcx_alf_statistics_picture(int pic_w, int pic_h, int bit_depth, int n_bins, const uint16_t *const org[3], const uint16_t *const rec[3],
+                                           int64_t *luma, int64_t *chroma, int device)
+{
+  if (!org || !rec || !luma) return fail(VVCX_ERR_ARG, "null argument");
+  for (int c = 0; c < 3; c++) if (!org[c] || !rec[c]) return fail(VVCX_ERR_ARG, "null plane");
+  if (pic_w < 8 || pic_h < 8 || (pic_w & 7) || (pic_h & 7) || pic_w > 16384 || pic_h > 16384 || bit_depth < 8 || bit_depth > 12) return fail(VVCX_ERR_ARG, "vvcx_alf_statistics_picture: picture size / bit depth");
+  if (n_bins != 1 && n_bins != 4) return fail(VVCX_ERR_ARG, "vvcx_alf_statistics_picture: %d clipping bins (1 or 4)", n_bins);
+  const int cw = (pic_w + 127) / 128, chh = (pic_h + 127) / 128, nctu = cw * chh;
+  ON_DEVICE(device);
+  DevBuf<uint16_t> planes; DevBuf<VxFrameDev> frame; DevBuf<long long> luma_d, chroma_d;
+  const size_t ny = (size_t) pic_w * pic_h, ncs = ny >> 2, per = ny + 2 * ncs;
+  const size_t nl = (size_t) nctu * 25 * alf_stat_size(n_bins, 13), nch = (size_t) nctu * 2 * alf_stat_size(n_bins, 7);
+  HIPCHK(planes.alloc(2 * per)); HIPCHK(frame.alloc(1)); HIPCHK(luma_d.alloc(nl));
+  if (chroma) HIPCHK(chroma_d.alloc(nch));
+  VxFrameDev fd; memset(&fd, 0, sizeof fd);
+  const size_t off[3] = { 0, ny, ny + ncs };
+  for (int c = 0; c < 3; c++) {
+    fd.org[c] = planes.p + off[c]; fd.rec[c] = planes.p + per + off[c]; fd.stride[c] = c ? pic_w >> 1 : pic_w;
+    HIPCHK(hipMemcpy(planes.p + off[c], org[c], (c ? ncs : ny) * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(planes.p + per + off[c], rec[c], (c ? ncs : ny) * 2, hipMemcpyHostToDevice));
+  }
+  HIPCHK(hipMemcpy(frame.p, &fd, sizeof fd, hipMemcpyHostToDevice));
+  VxAlfStatParams p; memset(&p, 0, sizeof p);
+  p.frames = frame.p; p.luma = luma_d.p; p.chroma = chroma ? chroma_d.p : nullptr; p.frame_first = 0;
+  p.pic_w = pic_w; p.pic_h = pic_h; p.ctus_w = cw; p.ctus_h = chh; p.bit_depth = bit_depth;
+  alf_stats_launch(p, 1, n_bins, 2, 0);
+  HIPCHK(hipGetLastError()); HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(luma, luma_d.p, nl * sizeof(long long), hipMemcpyDeviceToHost));
+  if (chroma) HIPCHK(hipMemcpy(chroma, chroma_d.p, nch * sizeof(long long), hipMemcpyDeviceToHost));
+  return VVCX_OK;
+}
+extern "C" int vvcx_alf_statistics_bound_frames(vvcx_handle *h, int frame_first, int n, int n_bins, int64_t *luma, int64_t *chroma, void *hip_stream)
+{
+  NOT_PENDING(h);
+  if (!h || !luma) return fail(VVCX_ERR_ARG, "null argument");
+  if (!h->n_frames || !h->have_slice) return fail(VVCX_ERR_STATE, "no bound frames / slice");
+  if (n_bins != 1 && n_bins != 4) return fail(VVCX_ERR_ARG, "vvcx_alf_statistics_bound_frames: %d clipping bins (1 or 4)", n_bins);
+  if (frame_first < 0 || n < 1 || frame_first > h->n_frames - n) return fail(VVCX_ERR_ARG, "vvcx_alf_statistics_bound_frames: frames %d .. %d of %d", frame_first, frame_first + n - 1, h->n_frames);
+  if (h->lmcs_on) return fail(VVCX_ERR_UNSUPPORTED, "ALF statistics of an LMCS slice: the handle keeps the mapped original only");
+  if (const int rc = require_all_coded(h, "the ALF statistics")) return rc;
+  const int nctu = h->ctus_w * h->ctus_h;
+  const size_t nl = (size_t) n * nctu * 25 * alf_stat_size(n_bins, 13), nch = (size_t) n * nctu * 2 * alf_stat_size(n_bins, 7);
+  const bool wantC = chroma && h->cfg.chroma;
+  ON_DEVICE(h->cfg.device);
+  hipStream_t stream = (hipStream_t) hip_stream;
+  HIPCHK(h->alf_stat_luma_d.reserve(nl));
+  if (wantC) HIPCHK(h->alf_stat_chroma_d.reserve(nch));
+  VxAlfStatParams p; memset(&p, 0, sizeof p);
+  p.frames = h->frames_d.p; p.luma = h->alf_stat_luma_d.p; p.chroma = wantC ? h->alf_stat_chroma_d.p : nullptr; p.frame_first = frame_first;
+  p.pic_w = h->cfg.pic_w; p.pic_h = h->cfg.pic_h; p.ctus_w = h->ctus_w; p.ctus_h = h->ctus_h; p.bit_depth = h->cfg.bit_depth;
+  HIPCHK(hipEventRecord(h->ev0, stream));
+  alf_stats_launch(p, n, n_bins, h->cfg.bit_depth == 8 ? 1 : 2, stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(h->ev1, stream));
+  HIPCHK(hipMemcpyAsync(luma, h->alf_stat_luma_d.p, nl * sizeof(long long), hipMemcpyDeviceToHost, stream));
+  if (wantC) HIPCHK(hipMemcpyAsync(chroma, h->alf_stat_chroma_d.p, nch * sizeof(long long), hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  HIPCHK(hipEventElapsedTime(&h->last_alf_stats_ms, h->ev0, h->ev1));
+  if (chroma && !wantC) memset(chroma, 0, nch * sizeof(int64_t));      // a handle without chroma
+  return VVCX_OK;
+}
+extern "C" float vvcx_last_alf_stats_ms(const vvcx_handle *h) { return h ? h->last_alf_stats_ms : 0.f; }
+
+// ---- the filter decision for ONE picture from bin 0 of its statistics: linear filters only (see include/vvcx.h for what is in and out of scope and for the bit count).
+// The structure is the reference's (ALFProcess 661, mergeClasses 2344, deriveFilterCoeffs 2158, deriveCoeffQuant 2279, deriveCtbAlfEnableFlags 834); the code is this
+// project's.  A filter c (taps without the centre, 7 fractional bits) on statistics (E, y, pixAcc) predicts the squared error  pixAcc - 2 c.y / 128 + c.E.c / 128^2.
+namespace {
+struct AlfCov {
+  double E[12][12], y[12], pix;
+  void clear() { memset(this, 0, sizeof *this); }
+  // bin 0 of one (CTU, class) block of the statistics arrays: nc x nc | .. | y | .. | pixAcc; the centre row / column (nc - 1) is left out
+  void add(const int64_t *s, int nb, int nc)
+  {
+    const int64_t *ys = s + (size_t) nb * nb * nc * nc;
+    for (int k = 0; k < nc - 1; k++) { for (int l = 0; l < nc - 1; l++) E[k][l] += (double) s[k * nc + l]; y[k] += (double) ys[k]; }
+    pix += (double) ys[(size_t) nb * nc];
+  }
+  void add(const AlfCov &o, int n) { for (int k = 0; k < n; k++) { for (int l = 0; l < n; l++) E[k][l] += o.E[k][l]; y[k] += o.y[k]; } pix += o.pix; }
+  double err_q(const int *q, int n) const
+  {
+    double a = 0, b = 0;
+    for (int k = 0; k < n; k++) { a += q[k] * y[k]; double r = 0; for (int l = 0; l < n; l++) r += E[k][l] * q[l]; b += q[k] * r; }
+    return pix - a / 64. + b / 16384.;
+  }
+};
+// Cholesky solve of (E + eps I) c = y; false when a pivot is not positive
+static bool alf_chol(const AlfCov &s, int n, double eps, double *c)
+{
+  double L[12][12], z[12], dmax = 0;
+  for (int k = 0; k < n; k++) dmax = std::max(dmax, s.E[k][k] + eps);
+  for (int i = 0; i < n; i++) for (int j = 0; j <= i; j++) {
+    double v = s.E[i][j] + (i == j ? eps : 0.);
+    for (int k = 0; k < j; k++) v -= L[i][k] * L[j][k];
+    if (i == j) { if (!(v > 1e-12 * dmax)) return false; L[i][i] = std::sqrt(v); } else L[i][j] = v / L[j][j];
+  }
+  for (int i = 0; i < n; i++) { double v = s.y[i]; for (int k = 0; k < i; k++) v -= L[i][k] * z[k]; z[i] = v / L[i][i]; }
+  for (int i = n - 1; i >= 0; i--) { double v = z[i]; for (int k = i + 1; k < n; k++) v -= L[k][i] * c[k]; c[i] = v / L[i][i]; }
+  return true;
+}
+// least-squares coefficients: plain, then with a growing multiple of the mean diagonal on the diagonal while the matrix is singular; zero when nothing helps
+static void alf_solve(const AlfCov &s, int n, double *c)
+{
+  double tr = 0; for (int k = 0; k < n; k++) tr += s.E[k][k];
+  for (int k = 0; k < n; k++) c[k] = 0;
+  if (!(tr > 0)) return;
+  if (alf_chol(s, n, 0., c)) return;
+  for (double rel = 1e-10; rel < 1.; rel *= 100.) if (alf_chol(s, n, rel * tr / n, c)) return;
+  for (int k = 0; k < n; k++) c[k] = 0;
+}
+// the least error any real filter reaches on these statistics
+static double alf_ls_error(const AlfCov &s, int n) { double c[12], a = 0; alf_solve(s, n, c); for (int k = 0; k < n; k++) a += c[k] * s.y[k]; return s.pix - a; }
+// integer coefficients (7 fractional bits, -128 .. 127): rounding, then single steps of one coefficient while the predicted error falls; the zero filter if that is better
+static double alf_quant(const AlfCov &s, int n, int *q)
+{
+  double c[12]; alf_solve(s, n, c);
+  for (int k = 0; k < n; k++) q[k] = (int) std::min(127., std::max(-128., std::floor(c[k] * 128. + .5)));
+  double best = s.err_q(q, n);
+  for (int pass = 0; pass < 64; pass++) {
+    bool moved = false;
+    for (int k = 0; k < n; k++) for (int st = -1; st <= 1; st += 2) {
+      if (q[k] + st < -128 || q[k] + st > 127) continue;
+      q[k] += st;
+      const double e = s.err_q(q, n);
+      if (e < best) { best = e; moved = true; } else q[k] -= st;
+    }
+    if (!moved) break;
+  }
+  if (!(best < s.pix)) { for (int k = 0; k < n; k++) q[k] = 0; best = s.pix; }
+  return best;
+}
+static int alf_ue_bits(int v) { int b = 1; for (v++; v > 1; v >>= 1) b += 2; return b; }      // ue(v)
+static int alf_coeff_bits(const int *q, int n) { int b = 0; for (int k = 0; k < n; k++) b += alf_ue_bits(q[k] < 0 ? -q[k] : q[k]) + (q[k] != 0); return b; }
+struct AlfLuma { int n; uint8_t map[25]; int q[25][12]; double dist; int bits; };
+// merge the classes greedily from 25 groups to 1 (always the pair whose merge raises the least-squares error least), then the filter count <= max_filters with the least
+// predicted distortion + lambda * bits
+static void alf_derive_luma(const AlfCov *cls, double lambda, int max_filters, AlfLuma &best)
+{
+  AlfCov grp[25]; double gerr[25]; int of[25]; bool alive[25];
+  static thread_local uint8_t maps[26][25];
+  for (int c = 0; c < 25; c++) { grp[c] = cls[c]; gerr[c] = alf_ls_error(grp[c], 12); of[c] = c; alive[c] = true; }
+  for (int n = 25; n >= 1; n--) {
+    int idx[25], m = 0;
+    for (int g = 0; g < 25; g++) if (alive[g]) idx[g] = m++;
+    for (int c = 0; c < 25; c++) maps[n][c] = (uint8_t) idx[of[c]];
+    if (n == 1) break;
+    int bi = -1, bj = -1; double bd = 0, be = 0;
+    for (int i = 0; i < 25; i++) if (alive[i]) for (int j = i + 1; j < 25; j++) if (alive[j]) {
+      AlfCov t = grp[i]; t.add(grp[j], 12);
+      const double e = alf_ls_error(t, 12), d = e - gerr[i] - gerr[j];
+      if (bi < 0 || d < bd) { bi = i; bj = j; bd = d; be = e; }
+    }
+    grp[bi].add(grp[bj], 12); gerr[bi] = be; alive[bj] = false;
+    for (int c = 0; c < 25; c++) if (of[c] == bj) of[c] = bi;
+  }
+  bool have = false;
+  for (int n = std::min(25, std::max(1, max_filters)); n >= 1; n--) {
+    AlfLuma t; t.n = n; t.dist = 0; memcpy(t.map, maps[n], 25);
+    int mapBits = 0; for (int v = n - 1; v > 0; v >>= 1) mapBits++;
+    t.bits = 1 + alf_ue_bits(n - 1) + (n > 1 ? 25 * mapBits : 0);
+    for (int g = 0; g < n; g++) {
+      AlfCov s; s.clear();
+      for (int c = 0; c < 25; c++) if (t.map[c] == g) s.add(cls[c], 12);
+      t.dist += alf_quant(s, 12, t.q[g]); t.bits += alf_coeff_bits(t.q[g], 12);
+    }
+    if (!have || t.dist + lambda * t.bits < best.dist + lambda * best.bits) { best = t; have = true; }
+  }
+}
+}      // namespace
+
+extern "C" int vvcx_alf_decide(int pic_w, int pic_h, int bit_depth, int chroma, int n_bins, const int64_t *luma, const int64_t *chroma_stats,
+                               const double lambda[3], int max_luma_filters, vvcx_alf_aps *aps, vvcx_alf_slice *slice, vvcx_alf_ctu *ctus)
+{
+  if (!luma || !lambda || !aps || !slice || !ctus || (chroma && !chroma_stats)) return fail(VVCX_ERR_ARG, "null argument");
+  if (pic_w < 8 || pic_h < 8 || (pic_w & 7) || (pic_h & 7) || pic_w > 16384 || pic_h > 16384 || bit_depth < 8 || bit_depth > 12 || (n_bins != 1 && n_bins != 4) ||
+      max_luma_filters < 1 || max_luma_filters > 25 || !(lambda[0] >= 0) || !(lambda[1] >= 0) || !(lambda[2] >= 0))
+    return fail(VVCX_ERR_ARG, "vvcx_alf_decide: picture size / bit depth / bins / filter count / lambdas");
+  const int nctu = ((pic_w + 127) / 128) * ((pic_h + 127) / 128), nb = n_bins;
+  const size_t szl = alf_stat_size(nb, 13), szc = alf_stat_size(nb, 7);
+  memset(aps, 0, sizeof *aps); memset(slice, 0, sizeof *slice); memset(ctus, 0, sizeof *ctus * (size_t) nctu);
+  slice->n_luma_aps = 1; slice->luma_aps[0] = 0; slice->chroma_aps = -1;
+  aps->num_luma_filters = 1;
+  for (int a = 0; a < nctu; a++) ctus[a].set = 16;
+  // ---- luma: filters from all CTUs, the CTUs' flags against them, the filters once more from the enabled CTUs
+  {
+    std::vector<AlfCov> cc((size_t) nctu * 25);
+    for (int a = 0; a < nctu; a++) for (int c = 0; c < 25; c++) { AlfCov &s = cc[(size_t) a * 25 + c]; s.clear(); s.add(luma + ((size_t) a * 25 + c) * szl, nb, 13); }
+    std::vector<uint8_t> on((size_t) nctu, 1);
+    AlfLuma fl; int n_on = nctu; double gain = 0;
+    for (int round = 0; round < 2 && n_on; round++) {
+      AlfCov cls[25];
+      for (int c = 0; c < 25; c++) { cls[c].clear(); for (int a = 0; a < nctu; a++) if (on[(size_t) a]) cls[c].add(cc[(size_t) a * 25 + c], 12); }
+      alf_derive_luma(cls, lambda[0], max_luma_filters, fl);
+      if (round == 0) {
+        n_on = 0;
+        for (int a = 0; a < nctu; a++) {
+          double d_on = 0, d_off = 0;
+          for (int c = 0; c < 25; c++) { const AlfCov &s = cc[(size_t) a * 25 + c]; d_on += s.err_q(fl.q[fl.map[c]], 12); d_off += s.pix; }
+          on[(size_t) a] = d_on + lambda[0] * 1. < d_off;      // an enabled CTU codes one more bin (alf_use_aps_flag)
+          n_on += on[(size_t) a];
+        }
+      }
+    }
+    if (n_on) {
+      for (int a = 0; a < nctu; a++) if (on[(size_t) a]) {
+        for (int c = 0; c < 25; c++) { const AlfCov &s = cc[(size_t) a * 25 + c]; gain += s.pix - s.err_q(fl.q[fl.map[c]], 12); }
+        gain -= lambda[0];
+      }
+      if (!(gain > lambda[0] * fl.bits)) n_on = 0;      // the parameter set costs more than the filter gains: luma stays unfiltered
+    }
+    if (n_on) {
+      aps->num_luma_filters = fl.n;
+      for (int c = 0; c < 25; c++) aps->class_to_filter[c] = fl.map[c];
+      for (int g = 0; g < fl.n; g++) for (int k = 0; k < 12; k++) aps->luma_coeff[g][k] = (int16_t) fl.q[g][k];
+      for (int a = 0; a < nctu; a++) ctus[a].flag[0] = on[(size_t) a];
+    }
+  }
+  // ---- chroma: one alternative for both components, flags per component
+  if (chroma) {
+    std::vector<AlfCov> cc((size_t) nctu * 2);
+    for (size_t i = 0; i < cc.size(); i++) { cc[i].clear(); cc[i].add(chroma_stats + i * szc, nb, 7); }
+    std::vector<uint8_t> on(cc.size(), 1);
+    int q[6] = { 0 }, n_on = (int) cc.size();
+    for (int round = 0; round < 2 && n_on; round++) {
+      AlfCov s; s.clear();
+      for (size_t i = 0; i < cc.size(); i++) if (on[i]) s.add(cc[i], 6);
+      alf_quant(s, 6, q);
+      if (round == 0) { n_on = 0; for (size_t i = 0; i < cc.size(); i++) { on[i] = cc[i].err_q(q, 6) < cc[i].pix; n_on += on[i]; } }      // one alternative: a CTU codes its flag only
+    }
+    double gain = 0;
+    for (size_t i = 0; i < cc.size(); i++) if (on[i]) gain += cc[i].pix - cc[i].err_q(q, 6);
+    const int bits = 1 + alf_ue_bits(0) + alf_coeff_bits(q, 6);
+    if (n_on && gain > .5 * (lambda[1] + lambda[2]) * bits) {      // the parameter set's bits weigh with the mean of the two chroma lambdas
+      slice->chroma_aps = 0; aps->num_chroma_alt = 1;
+      for (int k = 0; k < 6; k++) aps->chroma_coeff[0][k] = (int16_t) q[k];
+      for (size_t i = 0; i < cc.size(); i++) ctus[i >> 1].flag[1 + (i & 1)] = on[i];
+    }
+  }
+  return VVCX_OK;
+}
 
 // the same two kernels on a picture the caller describes by a CU table (host memory in, host memory out): the unit maps the kernels read are built here from the rows
 extern "C" int vvcx_deblock_cu_table(int pic_w, int pic_h, int bit_depth, int qp, int qp_cb, int qp_cr, int beta_offset_div2, int tc_offset_div2,

@@ -136,6 +136,15 @@ struct VxAlfParams {
   int32_t pic_w, pic_h, ctus_w, ctus_h, bit_depth, chroma;
 };
 
+// ALF encoder statistics (vvcx_alf_stats.hip): the covariance sums of frames frame_first .. per (CTU, class); nc = 13 (luma) / 7 (chroma) coefficients, nb = n_bins
+struct VxAlfStatParams {
+  const VxFrameDev *frames;
+  long long *luma;                // [frame][ctu][25][nb*nb*169 + nb*13 + 1]: E | y | pixAcc
+  long long *chroma;              // [frame][ctu][2][nb*nb*49 + nb*7 + 1]; NULL: luma only
+  int32_t frame_first, pic_w, pic_h, ctus_w, ctus_h, bit_depth;
+  int32_t clip[2][4];             // clipping value of bin b: luma, chroma
+};
+
 // per-stream scratch layout (bytes)
 #define VXD_STORE_REC   (128 * 128 * 2)
 #define VXD_STORE_UNITS (32 * 32 * (int) sizeof(VxUnit))

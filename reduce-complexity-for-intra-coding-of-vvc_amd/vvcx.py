@@ -169,6 +169,16 @@ class AlfAps(C.Structure):
                 a.chroma_coeff[t][k] = int(row[636 + t * 6 + k]); a.chroma_clip_idx[t][k] = int(row[684 + t * 6 + k])
         return a
 
+    def to_row(self):
+        """the row form back (what synth.alf_test_params hands out)"""
+        row = np.zeros(732, np.int32)
+        row[0] = self.num_luma_filters; row[26] = self.nonlinear_luma; row[627] = self.num_chroma_alt
+        row[1:26] = list(self.class_to_filter)
+        row[27:327] = np.array([list(r) for r in self.luma_coeff]).ravel(); row[327:627] = np.array([list(r) for r in self.luma_clip_idx]).ravel()
+        row[628:636] = list(self.nonlinear_chroma)
+        row[636:684] = np.array([list(r) for r in self.chroma_coeff]).ravel(); row[684:732] = np.array([list(r) for r in self.chroma_clip_idx]).ravel()
+        return row
+
 
 class AlfSlice(C.Structure):
     _fields_ = [("n_luma_aps", C.c_int32), ("luma_aps", C.c_int32 * 8), ("chroma_aps", C.c_int32)]
@@ -197,6 +207,40 @@ def alf_picture(planes, bit_depth, prm, want_classes=False, device=0, lib_path=N
     L.vvcx_alf_picture.argtypes = [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     _chk(L, L.vvcx_alf_picture(w, h, bit_depth, C.addressof(aps), len(aps), C.addressof(sl), ctu.ctypes.data, out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data, cls.ctypes.data, device))
     return (out, cls) if want_classes else out
+
+
+def alf_stat_sizes(n_bins):
+    """int64 values per (CTU, class) of the luma statistics and per (CTU, component) of the chroma ones: E | y | pixAcc"""
+    return n_bins * n_bins * 169 + n_bins * 13 + 1, n_bins * n_bins * 49 + n_bins * 7 + 1
+
+
+def alf_statistics_picture(org, rec, bit_depth, n_bins=1, device=0, lib_path=None):
+    """vvcx_alf_statistics_picture: the ALF encoder's covariance statistics of one picture (three original planes, three planes as the ALF filter would read them) ->
+    (luma int64 [ctus, 25, nb*nb*169 + nb*13 + 1], chroma int64 [ctus, 2, nb*nb*49 + nb*7 + 1]), each block in the order E[b0][b1][k][l], y[b][k], pixAcc"""
+    L = load_library(lib_path)
+    o = [np.ascontiguousarray(p.astype(np.uint16)) for p in org]; r = [np.ascontiguousarray(p.astype(np.uint16)) for p in rec]
+    h, w = r[0].shape
+    nctu = ((w + 127) // 128) * ((h + 127) // 128)
+    szl, szc = alf_stat_sizes(n_bins if n_bins in (1, 4) else 1)
+    luma = np.zeros((nctu, 25, szl), np.int64); chroma = np.zeros((nctu, 2, szc), np.int64)
+    op = (C.c_void_p * 3)(*[p.ctypes.data for p in o]); rp = (C.c_void_p * 3)(*[p.ctypes.data for p in r])
+    L.vvcx_alf_statistics_picture.argtypes = [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_int]
+    _chk(L, L.vvcx_alf_statistics_picture(w, h, bit_depth, n_bins, op, rp, luma.ctypes.data, chroma.ctypes.data, device))
+    return luma, chroma
+
+
+def alf_decide(luma, chroma, width, height, bit_depth, lambdas, n_bins=1, max_luma_filters=25, lib_path=None):
+    """vvcx_alf_decide: linear ALF filters and per-CTU flags of one picture from its statistics (chroma None: luma only) -> a dict of the form synth.alf_test_params
+    hands out and alf_picture / alf_bound_frames take: aps [1, 732], luma_aps [0], chroma_aps 0 or -1, ctu [ctus, 6]"""
+    L = load_library(lib_path)
+    lu = np.ascontiguousarray(luma, np.int64); ch = None if chroma is None else np.ascontiguousarray(chroma, np.int64)
+    lam = np.ascontiguousarray(lambdas, np.float64)
+    nctu = ((width + 127) // 128) * ((height + 127) // 128)
+    aps = AlfAps(); sl = AlfSlice(); ctu = np.zeros((nctu, 6), np.int8)
+    L.vvcx_alf_decide.argtypes = [C.c_int] * 5 + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3
+    _chk(L, L.vvcx_alf_decide(width, height, bit_depth, int(ch is not None), n_bins, lu.ctypes.data, None if ch is None else ch.ctypes.data, lam.ctypes.data,
+                              int(max_luma_filters), C.addressof(aps), C.addressof(sl), ctu.ctypes.data))
+    return dict(aps=aps.to_row()[None, :], luma_aps=[int(sl.luma_aps[k]) for k in range(sl.n_luma_aps)], chroma_aps=int(sl.chroma_aps), ctu=ctu.astype(np.int32))
 
 
 def lmcs_analyze_device(ptrs, strides, width, height, bit_depth, qp, update_ctrl=1, lib_path=None):
@@ -314,6 +358,19 @@ class VvcxEncoder:
         self.L.vvcx_last_alf_ms.argtypes = [C.c_void_p]
         self._chk(self.L.vvcx_alf_bound_frames(self.h, C.addressof(aps), len(aps), C.addressof(sl), ctu.ctypes.data, None))
         return float(self.L.vvcx_last_alf_ms(self.h))
+
+    def alf_statistics_bound_frames(self, frame_first=0, n=None, n_bins=1, want_chroma=True):
+        """vvcx_alf_statistics_bound_frames on bound pictures frame_first .. frame_first + n - 1 -> (luma int64 [n, ctus, 25, .], chroma int64 [n, ctus, 2, .] or None,
+        kernel ms); the blocks as alf_statistics_picture returns them"""
+        n = self.n_frames - frame_first if n is None else n
+        szl, szc = alf_stat_sizes(n_bins if n_bins in (1, 4) else 1)
+        luma = np.zeros((max(n, 0), self.ctus_per_frame, 25, szl), np.int64)
+        chroma = np.zeros((max(n, 0), self.ctus_per_frame, 2, szc), np.int64) if want_chroma else None
+        self.L.vvcx_alf_statistics_bound_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        self.L.vvcx_last_alf_stats_ms.restype = C.c_float
+        self.L.vvcx_last_alf_stats_ms.argtypes = [C.c_void_p]
+        self._chk(self.L.vvcx_alf_statistics_bound_frames(self.h, int(frame_first), int(n), int(n_bins), luma.ctypes.data, None if chroma is None else chroma.ctypes.data, None))
+        return luma, chroma, float(self.L.vvcx_last_alf_stats_ms(self.h))
 
     def get_levels(self, frame):
         """quantised levels of the coded picture: three int16 planes (Y, Cb, Cr)"""
