@@ -380,6 +380,26 @@ int  vvcx_transform_skip_batch(const int16_t *resi, int w, int h, int bit_depth,
  * sub-partition after all-zero ones, EL/CABACWriter.cpp:3574-3600), dequantisation, inverse, reconstruction over pred; qp = slice QP + QpBDOffset */
 int  vvcx_isp_tu_batch(const int16_t *org, const int16_t *pred, int tw, int th, int bit_depth, int qp, double lambda, int prev_cbf, int cbf_inferred,
                        const uint16_t *s0, const uint16_t *s1, int n, int16_t *lev, int16_t *rec, uint64_t *sse, uint8_t *cbf, int device);
+/* residual coding of n blocks of w x h levels (back to back, stride w; every block with at least one level, none in the area the block's transform zeroes): ≙
+ * CABACWriter::residual_coding (EL/CABACWriter.cpp:3773-3883, last_sig_coeff 4102-4160, residual_coding_subblock 4164-4304) or, for mts_idx 1, residual_codingTS
+ * (4306-4555).  Every block starts from the same states s0 / s1 of the 386 context models.  comp 0 luma / 1 chroma; tools: VVCX_TOOL_DEPQUANT runs the quantiser's state
+ * machine (context set of sig_coeff_flag, zero position of the bypass pass); ts_allowed / mts_allowed = TU::isTSAllowed / TU::isMTSAllowed of the block (luma up to
+ * 32 x 32, not in an ISP CU); mts_idx = tu.mtsIdx: 0, 1 (transform skip, sides 4..32) or 2..5 (a 32-point side then codes 16).  The path holds this syntax in four
+ * forms, which must agree:
+ *   form 0  the single-lane estimator of the controller (mts_idx 1: the single-lane residual_codingTS)
+ *   form 1  the lane-parallel estimator on levels staged in the wave's LDS slot (blocks of at most 256 levels, not mts_idx 1)
+ *   form 2  the lane-parallel estimator on levels in device memory (not mts_idx 1)
+ *   form 3  the writer: a fresh arithmetic coder, mts_coding (3885-3941) of a luma block as the final pass writes it, the levels, a terminating bin of 1, finish and
+ *           byte alignment; block i's bytes at bytes + i * bytes_cap, their count in nbytes[i]
+ * Out per block: the fractional bits (2^-15; forms 0..2 the levels alone, form 3 including the transform indices), the end states of all 386 models
+ * (s0_out / s1_out [n][386]), rc_last = the last significant scan position (-1 for mts_idx 1).  bytes / nbytes may be null for forms 0..2. */
+int  vvcx_residual_coding_batch(const int16_t *lev, int w, int h, int n, int comp, uint32_t tools, int ts_allowed, int mts_allowed, int mts_idx,
+                                const uint16_t *s0, const uint16_t *s1, int form, uint64_t *frac_bits, uint16_t *s0_out, uint16_t *s1_out, int32_t *rc_last,
+                                uint8_t *bytes, int bytes_cap, int32_t *nbytes, int device);
+/* the arithmetic coder (≙ BinEncoder_Std, EL/BinEncoder.cpp:106-420) over an operation string, from the I-slice context models at qp: ops[i] = {kind, a, b}:
+ * kind 0 = bin b on context model a (the reference's flat index; a model the library keeps), 1 = b bypass bins (1..32) of value a, MSB first, 2 = terminating bin a.
+ * Ends with finish and byte alignment; the bytes go to out (room for cap), their count to nbytes */
+int  vvcx_arith_encode(int qp, const int32_t *ops, int nops, uint8_t *out, int cap, int *nbytes, int device);
 /* coefficient scan (diagonal, grouped) of a w x h block: idx[min(w,32) * min(h,32)] raster offsets in scan order */
 int  vvcx_scan_order(int w, int h, uint16_t *idx, int device);
 /* ≙ BIN/TEST.py GetPartition(C0..C25, 2): the forest of vvcx_set_forest on n rows of 26 int32 features (host pointers) → class per row */

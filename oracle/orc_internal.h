@@ -29,6 +29,9 @@ static inline void orc_bs_write(orc_arith *a, uint32_t v, int nbits)           /
     if (a->bit_n == 8) { if (a->n < a->cap) a->out[a->n] = (uint8_t) a->bit_acc; a->n++; a->bit_acc = 0; a->bit_n = 0; }
   }
 }
+/* how buffered bytes resolved (orc_arith_counters): {times, longest run of buffered bytes} for writeOut without / with a carry, finish with / without a carry */
+extern int64_t orc_arith_cnt[8];
+static inline void orc_arith_note(int way, int run) { if (run > 0) { orc_arith_cnt[2 * way]++; if (run > orc_arith_cnt[2 * way + 1]) orc_arith_cnt[2 * way + 1] = run; } }
 static inline void orc_arith_start(orc_arith *a) { a->low = 0; a->range = 510; a->buffered_byte = 0xff; a->num_buffered = 0; a->bits_left = 23; }   /* 122-131 */
 static inline void orc_arith_write_out(orc_arith *a)                            /* writeOut 341-371 */
 {
@@ -38,6 +41,7 @@ static inline void orc_arith_write_out(orc_arith *a)                            
   if (lead == 0xff) a->num_buffered++;
   else if (a->num_buffered > 0) {
     const uint32_t carry = lead >> 8;
+    orc_arith_note(carry ? 1 : 0, a->num_buffered);
     uint32_t byte = a->buffered_byte + carry;
     a->buffered_byte = lead & 0xff;
     orc_bs_write(a, byte, 8);
@@ -67,10 +71,12 @@ static inline void orc_arith_trm(orc_arith *a, unsigned bin)                    
 static inline void orc_arith_finish(orc_arith *a)                               /* finish 133-158 */
 {
   if (a->low >> (32 - a->bits_left)) {
+    orc_arith_note(2, a->num_buffered);
     orc_bs_write(a, a->buffered_byte + 1, 8);
     while (a->num_buffered > 1) { orc_bs_write(a, 0x00, 8); a->num_buffered--; }
     a->low -= 1u << (32 - a->bits_left);
   } else {
+    orc_arith_note(3, a->num_buffered);
     if (a->num_buffered > 0) orc_bs_write(a, a->buffered_byte, 8);
     while (a->num_buffered > 1) { orc_bs_write(a, 0xff, 8); a->num_buffered--; }
   }

@@ -985,3 +985,7 @@ int orc_trquant_lfnst(const uint16_t *s0, const uint16_t *s1, const int16_t *res
   free(coef);
   return abs_sum;
 }
+
+/* how the arithmetic coder's buffered bytes resolved since the last read-out (orc_internal.h orc_arith_note) */
+int64_t orc_arith_cnt[8];
+void orc_arith_counters(int64_t *out) { memcpy(out, orc_arith_cnt, sizeof orc_arith_cnt); memset(orc_arith_cnt, 0, sizeof orc_arith_cnt); }

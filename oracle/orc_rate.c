@@ -72,10 +72,29 @@ static int tmpl_abs_sum(const cctx_t *c, const int16_t *coeff, int blk, int base
   if (posY < H - 1) { sum += abs(p[W]); if (posY < H - 2) sum += abs(p[W << 1]); }
   return imax(imin(sum - 5 * base, 31), 0);
 }
+/* branch counters of residual_coding (orc_residual_counters): plain statics, read and reset by the read-out */
+static int64_t RC_CNT[ORC_RC_COUNTERS];
+static int rc_pass = 2;                   /* which pass codes the remainder: 0 behind context-coded bins, 1 the bypass pass, 2 residual_codingTS (orc_ts.c) */
+static uint8_t rc_seen[ORC_NUM_CTX]; static int rc_run = -2, rc_distinct;      /* the models used inside the current aligned run of 64 scan positions */
+static void rc_run_end(void)
+{
+  if (rc_distinct > RC_CNT[ORC_RC_MAX_MODELS_IN_64]) RC_CNT[ORC_RC_MAX_MODELS_IN_64] = rc_distinct;
+  memset(rc_seen, 0, sizeof rc_seen); rc_distinct = 0; rc_run = -2;
+}
+/* a context-coded bin of residual_coding at scan position sp: the lane-parallel form of the device replays the bins of 64 positions at a time, grouped by model */
+static void rc_bin(orc_cabac *cb, unsigned bin, int ctx, int sp)
+{
+  if ((sp >> 6) != rc_run) { rc_run_end(); rc_run = sp >> 6; }
+  if (!rc_seen[ctx]) { rc_seen[ctx] = 1; rc_distinct++; }
+  orc_enc_bin(cb, bin, ctx);
+}
+void orc_residual_counters(int64_t *out) { memcpy(out, RC_CNT, sizeof RC_CNT); memset(RC_CNT, 0, sizeof RC_CNT); }
+
 /* EL/BinEncoder.cpp:444-472 (useLimitedPrefixLength forced true) */
 void orc_enc_rem_abs(orc_cabac *cb, unsigned bins, unsigned rice)
 {
   const unsigned thr = 5u << rice;
+  if (rice < 4) RC_CNT[ORC_RC_REM + (rc_pass * 4 + (int) rice) * 3 + (bins < thr ? 0 : ((bins >> rice) - 5 >= (1u << 12) - 1) ? 2 : 1)]++;
   if (bins < thr) {                                   /* unary prefix, then rice bits (EL/BinEncoder.cpp:222-229) */
     const unsigned length = (bins >> rice) + 1;
     orc_enc_bins_ep(cb, (1u << length) - 2, (int) length);
@@ -124,6 +143,7 @@ void orc_residual_coding_tu(orc_cabac *cb, const int16_t *coeff, int w, int h, i
   uint8_t sigGroupFlags[64] = { 0 };
   for (int sp = 0; sp < c.nscan; sp++) if (coeff[c.scan[sp]]) { scanPosLast = sp; sigGroupFlags[sp >> c.lcg] = 1; }
   if (scanPosLast < 0) return;   /* reference CHECKs; callers only come here with cbf = 1 */
+  rc_run_end();
   cb->last_scan_pos = scanPosLast;         /* read by the CU-level LFNST signalling (3837-3850) */
 
   /* last_sig_coeff (4102-4160) */
@@ -134,10 +154,10 @@ void orc_residual_coding_tu(orc_cabac *cb, const int16_t *coeff, int w, int h, i
     /* 4115-4126: with an explicit MTS pair a 32-point side only codes positions below 16 */
     const int maxX = ORC_GROUP_IDX[(zo && w == 32 ? 16 : imin(32, w)) - 1], maxY = ORC_GROUP_IDX[(zo && h == 32 ? 16 : imin(32, h)) - 1];
     int k;
-    for (k = 0; k < gx; k++) orc_enc_bin(cb, 1, ORC_CTX_LastX[c.ch] + c.last_off_x + (k >> c.last_sh_x));
-    if (gx < maxX) orc_enc_bin(cb, 0, ORC_CTX_LastX[c.ch] + c.last_off_x + (k >> c.last_sh_x));
-    for (k = 0; k < gy; k++) orc_enc_bin(cb, 1, ORC_CTX_LastY[c.ch] + c.last_off_y + (k >> c.last_sh_y));
-    if (gy < maxY) orc_enc_bin(cb, 0, ORC_CTX_LastY[c.ch] + c.last_off_y + (k >> c.last_sh_y));
+    for (k = 0; k < gx; k++) rc_bin(cb, 1, ORC_CTX_LastX[c.ch] + c.last_off_x + (k >> c.last_sh_x), scanPosLast);
+    if (gx < maxX) rc_bin(cb, 0, ORC_CTX_LastX[c.ch] + c.last_off_x + (k >> c.last_sh_x), scanPosLast); else RC_CNT[ORC_RC_LAST_FULL_X]++;
+    for (k = 0; k < gy; k++) rc_bin(cb, 1, ORC_CTX_LastY[c.ch] + c.last_off_y + (k >> c.last_sh_y), scanPosLast);
+    if (gy < maxY) rc_bin(cb, 0, ORC_CTX_LastY[c.ch] + c.last_off_y + (k >> c.last_sh_y), scanPosLast); else RC_CNT[ORC_RC_LAST_FULL_Y]++;
     if (gx > 3) orc_enc_bins_ep(cb, (uint32_t) (posX - ORC_MIN_IN_GROUP[gx]), (gx - 2) >> 1);
     if (gy > 3) orc_enc_bins_ep(cb, (uint32_t) (posY - ORC_MIN_IN_GROUP[gy]), (gy - 2) >> 1);
   }
@@ -154,14 +174,15 @@ void orc_residual_coding_tu(orc_cabac *cb, const int16_t *coeff, int w, int h, i
     const int sigRight = (cgPosX + 1) < c.wg ? c.sig_group[cgPos + 1] : 0;
     const int sigLower = (cgPosY + 1) < c.hg ? c.sig_group[cgPos + c.wg] : 0;
     const int sigGroupCtx = ORC_CTX_SigCoeffGroup[c.ch] + (sigRight | sigLower);
-    if (zo && ((h == 32 && cgPosY >= (16 >> c.lch)) || (w == 32 && cgPosX >= (16 >> c.lcw)))) continue;   /* 3866-3877: sub-blocks of the zeroed area are not coded */
+    if (zo && ((h == 32 && cgPosY >= (16 >> c.lch)) || (w == 32 && cgPosX >= (16 >> c.lcw)))) { RC_CNT[ORC_RC_ZERO_OUT_SKIP]++; continue; }   /* 3866-3877: sub-blocks of the zeroed area are not coded */
     /* residual_coding_subblock (4164-4304) */
     const int isLast = (scanPosLast >> c.lcg) == sub, isNotFirst = sub != 0;
     const int firstSigPos = isLast ? scanPosLast : maxSub;
     int nextSigPos = firstSigPos;
     if (!isLast && isNotFirst) {
-      if (c.sig_group[cgPos]) orc_enc_bin(cb, 1, sigGroupCtx);
-      else { orc_enc_bin(cb, 0, sigGroupCtx); continue; }
+      RC_CNT[ORC_RC_GROUP_FLAG + 2 * (sigRight | sigLower) + c.sig_group[cgPos]]++;
+      if (c.sig_group[cgPos]) rc_bin(cb, 1, sigGroupCtx, maxSub);
+      else { rc_bin(cb, 0, sigGroupCtx, maxSub); continue; }
     }
     uint8_t ctxOffset[16];
     const int inferSigPos = nextSigPos != scanPosLast ? (isNotFirst ? minSub : -1) : nextSigPos;
@@ -173,9 +194,9 @@ void orc_residual_coding_tu(orc_cabac *cb, const int16_t *coeff, int w, int h, i
       const unsigned sigFlag = cf != 0;
       if (numNonZero || nextSigPos != inferSigPos) {
         const int ctx = sig_ctx(&c, coeff, blk, state);
-        orc_enc_bin(cb, sigFlag, ctx);
+        rc_bin(cb, sigFlag, ctx, nextSigPos);
         remRegBins--;
-      } else if (nextSigPos != scanPosLast) sig_ctx(&c, coeff, blk, state);
+      } else if (nextSigPos != scanPosLast) { sig_ctx(&c, coeff, blk, state); RC_CNT[ORC_RC_INFERRED_SIG]++; }
       if (sigFlag) {
         const int off = ctx_offset_abs(&c);
         ctxOffset[nextSigPos - minSub] = (uint8_t) off;
@@ -183,20 +204,22 @@ void orc_residual_coding_tu(orc_cabac *cb, const int16_t *coeff, int w, int h, i
         signPattern = (signPattern << 1) | (cf < 0);     /* 4218-4219: no shift before the very first coefficient, where it is 0 anyway */
         int rem = abs(cf) - 1;
         const unsigned gt1 = !!rem;
-        orc_enc_bin(cb, gt1, ORC_CTX_GtxFlag[c.ch + 2] + off);     /* greater1CtxIdAbs = m_gtxFlagCtxSet[1] */
+        rc_bin(cb, gt1, ORC_CTX_GtxFlag[c.ch + 2] + off, nextSigPos);     /* greater1CtxIdAbs = m_gtxFlagCtxSet[1] */
         remRegBins--;
         if (gt1) {
           rem -= 1;
-          orc_enc_bin(cb, rem & 1, ORC_CTX_ParFlag[c.ch] + off);
+          rc_bin(cb, rem & 1, ORC_CTX_ParFlag[c.ch] + off, nextSigPos);
           rem >>= 1;
           remRegBins--;
-          orc_enc_bin(cb, !!rem, ORC_CTX_GtxFlag[c.ch] + off);     /* greater2CtxIdAbs = m_gtxFlagCtxSet[0] */
+          rc_bin(cb, !!rem, ORC_CTX_GtxFlag[c.ch] + off, nextSigPos);     /* greater2CtxIdAbs = m_gtxFlagCtxSet[0] */
           remRegBins--;
         }
       }
       state = (stateTab >> ((state << 2) + ((cf & 1) << 1))) & 3;      /* 4247 */
     }
     const int firstPosMode2 = nextSigPos;
+    if (firstPosMode2 >= minSub && firstPosMode2 < firstSigPos) RC_CNT[ORC_RC_BUDGET_MID_GROUP]++;
+    rc_pass = 0;
     c.reg_bins = remRegBins;
     /* 2nd pass: Golomb-Rice remainders of context-coded positions (4260-4272) */
     for (int sp = firstSigPos; sp > firstPosMode2; sp--) {
@@ -208,19 +231,23 @@ void orc_residual_coding_tu(orc_cabac *cb, const int16_t *coeff, int w, int h, i
       }
     }
     /* 3rd pass: bypass-coded positions (4275-4294) */
+    rc_pass = 1;
     for (int sp = firstPosMode2; sp >= minSub; sp--) {
       const int blk = c.scan[sp];
       const unsigned absLevel = (unsigned) abs(coeff[blk]);
       const int sumAll = tmpl_abs_sum(&c, coeff, blk, 0);
       const unsigned rice = ORC_GORICE_PARS[sumAll], pos0 = ORC_GORICE_POS0[imax(0, state - 1) * 32 + sumAll];
       const unsigned rem = absLevel == 0 ? pos0 : absLevel <= pos0 ? absLevel - 1 : absLevel;
+      RC_CNT[ORC_RC_POS0 + 3 * state + (absLevel == 0 ? 0 : absLevel <= pos0 ? 1 : 2)]++;
       orc_enc_rem_abs(cb, rem, rice);
       state = (stateTab >> ((state << 2) + ((absLevel & 1) << 1))) & 3;
       if (absLevel) { numNonZero++; signPattern = (signPattern << 1) | (coeff[blk] < 0); }
     }
     (void) ctxOffset;
     orc_enc_bins_ep(cb, signPattern, numNonZero);    /* sign bits (4297-4303), no sign hiding */
+    rc_pass = 2;
   }
+  rc_run_end();
 }
 
 uint64_t orc_residual_bits(uint16_t *s0, uint16_t *s1, const int16_t *level, int w, int h, int is_chroma)
@@ -239,4 +266,21 @@ uint64_t orc_residual_bits_dq(uint16_t *s0, uint16_t *s1, const int16_t *level, 
   orc_residual_coding_mts(&c, level, w, h, is_chroma, mts_idx);
   memcpy(s0, c.s0, sizeof c.s0); memcpy(s1, c.s1, sizeof c.s1);
   return c.bits;
+}
+/* test entry of one TU's residual (tests/golden/residual_range.npz), from the states s0 / s1: write = 0: the levels alone on the estimator (the transform indices are the
+ * caller's: what the search adds per candidate); write = 1: a coder of its own: arith start, mts_coding + the levels (orc_residual_coding_tu), a terminating bin of 1,
+ * finish, byte alignment.  Out: the fractional bits, the end states, scanPosLast (-1 for transform skip); returns the bytes written (0 for write = 0; -1: out too small) */
+int orc_residual_leaf(const uint16_t *s0, const uint16_t *s1, const int16_t *level, int w, int h, int is_chroma, int dep_quant, int ts_allowed, int mts_allowed, int mts_idx, int write,
+                      uint64_t *bits, uint16_t *e0, uint16_t *e1, int *last, uint8_t *out, int cap)
+{
+  orc_cabac c; memset(&c, 0, sizeof c);
+  orc_arith aw; memset(&aw, 0, sizeof aw);
+  memcpy(c.s0, s0, sizeof c.s0); memcpy(c.s1, s1, sizeof c.s1);
+  c.dq = dep_quant; c.last_scan_pos = -1;
+  if (write) { aw.out = out; aw.cap = (size_t) cap; orc_arith_start(&aw); c.aw = &aw; }
+  orc_residual_coding_tu(&c, level, w, h, is_chroma, write ? ts_allowed : 0, write ? mts_allowed : 0, mts_idx);
+  if (write) { orc_arith_trm(&aw, 1); orc_arith_finish(&aw); orc_bs_write(&aw, 1, 1); while (aw.bit_n) orc_bs_write(&aw, 0, 1); }
+  *bits = c.bits; *last = mts_idx == 1 ? -1 : c.last_scan_pos;
+  memcpy(e0, c.s0, sizeof c.s0); memcpy(e1, c.s1, sizeof c.s1);
+  return !write ? 0 : aw.n > aw.cap ? -1 : (int) aw.n;
 }

@@ -149,6 +149,21 @@ void     orc_sao_counters(int64_t *out /* [ORC_SAO_COUNTERS] */);
 enum { ORC_ALF_CLIP_0, ORC_ALF_CLIP_MAX, ORC_ALF_CLIP_IDX_USED, ORC_ALF_CLIP_IDX_CUT = 6, ORC_ALF_VB_LUMA = 10, ORC_ALF_VB_CHROMA = 14, ORC_ALF_TRANSPOSE = 16, ORC_ALF_SET_CLASS = 20,
        ORC_ALF_COUNTERS = 420 };
 void     orc_alf_counters(int64_t *out /* [ORC_ALF_COUNTERS] */);
+/* Branch counters of residual_coding (orc_rate.c), read and reset like the filters': the regular-bin budget ran out inside a coefficient group that had begun with context-coded
+ * bins | remainder codes at ORC_RC_REM + (pass * 4 + Rice parameter) * 3 + form: pass 0 behind context-coded bins, 1 the bypass pass, 2 residual_codingTS; form 0 prefix below
+ * 5, 1 escape, 2 escape with the longest prefix (12, suffix 15) | bypass pass, per quantiser state s at ORC_RC_POS0 + 3 s: a zero coded as pos0, a level up to pos0 coded as
+ * level - 1, a level above pos0 | a significance that was inferred | coded_sub_block_flag at ORC_RC_GROUP_FLAG + 2 context + flag | last_sig_coeff prefix of full length (no
+ * terminating zero) in X, in Y | a coefficient group of the zeroed area of a 32-point MTS block skipped | not a count: the greatest number of distinct context models used by
+ * the bins of one aligned run of 64 scan positions (the device's lane-parallel form replays such a run grouped by model, 64 models per round) */
+enum { ORC_RC_BUDGET_MID_GROUP, ORC_RC_REM, ORC_RC_POS0 = ORC_RC_REM + 36, ORC_RC_INFERRED_SIG = ORC_RC_POS0 + 12, ORC_RC_GROUP_FLAG, ORC_RC_LAST_FULL_X = ORC_RC_GROUP_FLAG + 4,
+       ORC_RC_LAST_FULL_Y, ORC_RC_ZERO_OUT_SKIP, ORC_RC_MAX_MODELS_IN_64, ORC_RC_COUNTERS };
+void     orc_residual_counters(int64_t *out /* [ORC_RC_COUNTERS] */);
+/* the arithmetic coder's buffered bytes (a byte followed by 0xff bytes that wait for a possible carry): {times, longest run of buffered bytes} for each way they resolve:
+ * writeOut without a carry, writeOut with a carry, finish with a carry, finish without one */
+void     orc_arith_counters(int64_t *out /* [8] */);
+/* one TU's residual from given states: the estimator on the levels alone (write 0), or a coder of its own with the transform indices, a terminating bin and finish (write 1) */
+int      orc_residual_leaf(const uint16_t *s0, const uint16_t *s1, const int16_t *level, int w, int h, int is_chroma, int dep_quant, int ts_allowed, int mts_allowed, int mts_idx, int write,
+                           uint64_t *bits, uint16_t *e0, uint16_t *e1, int *last, uint8_t *out, int cap);
 /* the encoder's SAO statistics (EL/EncSampleAdaptiveOffset.cpp getStatistics, SAOLcuBoundary 0): out [ctu][component][type 0..4][count | diff][32] int64.  PARITY UNPINNED
  * for the region rules (see orc_sao.c) */
 int      orc_sao_statistics(int w, int h, int bit_depth, int tile_cols, int tile_rows, int lf_across_tiles, const int16_t *const org[3], const int16_t *const rec[3], int64_t *out);

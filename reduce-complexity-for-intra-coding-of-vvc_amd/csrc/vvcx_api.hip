@@ -27,6 +27,9 @@ extern "C" __global__ void vvcx_leaf_cabac_kernel(uint16_t *io, int ctx, const u
 extern "C" __global__ void vvcx_leaf_rdcost_kernel(VxParams p, const unsigned long long *bits, const unsigned long long *dist, int n, double *cost);
 extern "C" __global__ void vvcx_leaf_scan_kernel(int w, int h, uint16_t *idx);
 extern "C" __global__ void vvcx_leaf_forest_kernel(VxParams p, const int32_t *rows, int n, int32_t *out);
+extern "C" __global__ void vvcx_leaf_rc_kernel(VxParams p, const uint16_t *ctx, const int16_t *lev, int w, int h, int ch, int mts, int form, uint16_t *scan, uint16_t *ctx_out,
+                                               unsigned long long *out, uint8_t *bytes, uint32_t cap, uint32_t *nbytes);
+extern "C" __global__ void vvcx_leaf_arith_kernel(const uint16_t *ctx, const int32_t *ops, int nops, uint8_t *bytes, uint32_t cap, uint32_t *nbytes);
 struct VxMipCase { int32_t w, h, mode, bit_depth, ref_off, pred_off; };
 extern "C" __global__ void vvcx_leaf_mip_kernel(const VxMipCase *cases, const int16_t *refs, int16_t *preds);
 extern "C" __global__ void vvcx_sao_copy_kernel_u8(VxSaoParams p);
@@ -1970,6 +1973,98 @@ extern "C" int vvcx_transform_skip_batch(const int16_t *resi, int w, int h, int 
   HIPCHK(hipMemcpy(lev, dlev.p, bytes, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(resi_out, dout.p, bytes, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(o.data(), do2.p, (size_t) n * 8, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(frac_bits, dbits.p, (size_t) n * 8, hipMemcpyDeviceToHost));
   for (int i = 0; i < n; i++) { abs_sum[i] = o[(size_t) i * 2]; keep[i] = (uint8_t) o[(size_t) i * 2 + 1]; }
+  return VVCX_OK;
+}
+
+static void ctx_to_reference_order(const uint16_t *kept, uint16_t *s0, uint16_t *s1)      // the models the library keeps, back into arrays that hold the start states
+{
+  for (int k = 0; k < VXD_NUM_CTX; k++) { s0[VX_CTX_REF_INDEX[k]] = kept[k]; s1[VX_CTX_REF_INDEX[k]] = kept[VXD_NUM_CTX + k]; }
+}
+
+// ≙ CABACWriter::residual_coding (EL/CABACWriter.cpp:3773-3883) / residual_codingTS (4306-4555) of n blocks of levels, each from the same start states, in one of the
+// forms the path has; see include/vvcx.h
+extern "C" int vvcx_residual_coding_batch(const int16_t *lev, int w, int h, int n, int comp, uint32_t tools, int ts_allowed, int mts_allowed, int mts_idx,
+                                          const uint16_t *s0, const uint16_t *s1, int form, uint64_t *frac_bits, uint16_t *s0_out, uint16_t *s1_out, int32_t *rc_last,
+                                          uint8_t *bytes, int bytes_cap, int32_t *nbytes, int device)
+{
+  const bool shape = w >= 1 && h >= 1 && w <= 64 && h <= 64 && !(w & (w - 1)) && !(h & (h - 1)) && w * h >= 4;
+  if (!lev || !s0 || !s1 || !frac_bits || !s0_out || !s1_out || !rc_last || n < 0 || !shape || comp < 0 || comp > 1 || form < 0 || form > 3 || mts_idx < 0 || mts_idx > 5)
+    return fail(VVCX_ERR_ARG, "bad argument");
+  const bool small = w <= 32 && h <= 32;
+  if ((ts_allowed || mts_allowed || mts_idx) && (comp != 0 || !small)) return fail(VVCX_ERR_ARG, "transform indices belong to luma blocks of at most 32 x 32");
+  if ((mts_idx == 1 && (!ts_allowed || w < 4 || h < 4)) || (mts_idx > 1 && !mts_allowed)) return fail(VVCX_ERR_ARG, "mts_idx %d is not allowed for the block", mts_idx);
+  if (mts_idx == 1 && (form == 1 || form == 2)) return fail(VVCX_ERR_ARG, "transform-skip levels have no wave form");
+  if (form == 1 && w * h > VXD_BUF) return fail(VVCX_ERR_ARG, "form 1 takes blocks of at most %d levels", VXD_BUF);
+  if (form == 3 && (!bytes || !nbytes || bytes_cap <= 0)) return fail(VVCX_ERR_ARG, "form 3 needs a byte buffer");
+  const int P = w * h, zw = (mts_idx > 1 && w == 32) ? 16 : (mts_idx == 1 || w < 32) ? w : 32, zh = (mts_idx > 1 && h == 32) ? 16 : (mts_idx == 1 || h < 32) ? h : 32;
+  for (int i = 0; i < n; i++) {
+    bool any = false;
+    for (int y = 0; y < h; y++) for (int x = 0; x < w; x++) {
+      const int v = lev[(size_t) i * P + y * w + x];
+      if (v && (x >= zw || y >= zh)) return fail(VVCX_ERR_ARG, "block %d has a level in its zeroed area", i);
+      any |= v != 0;
+    }
+    if (!any) return fail(VVCX_ERR_ARG, "block %d has no level (residual coding needs cbf = 1)", i);
+  }
+  if (n == 0) return VVCX_OK;
+  ON_DEVICE(device);
+  const uint32_t cap = form == 3 ? (uint32_t) bytes_cap : 0;
+  DevBuf<int16_t> dlev; DevBuf<uint16_t> dctx, dscan, dco; DevBuf<unsigned long long> dout; DevBuf<uint8_t> dby; DevBuf<uint32_t> dnb;
+  HIPCHK(dlev.alloc((size_t) n * P)); HIPCHK(dctx.alloc(2 * VXD_NUM_CTX)); HIPCHK(dscan.alloc((size_t) n * 1024)); HIPCHK(dco.alloc((size_t) n * 2 * VXD_NUM_CTX));
+  HIPCHK(dout.alloc((size_t) n * 2)); HIPCHK(dby.alloc((size_t) n * cap + 1)); HIPCHK(dnb.alloc((size_t) n));
+  HIPCHK(hipMemcpy(dlev.p, lev, (size_t) n * P * 2, hipMemcpyHostToDevice));
+  { uint16_t kept[2 * VXD_NUM_CTX]; ctx_from_reference_order(s0, s1, kept); HIPCHK(hipMemcpy(dctx.p, kept, sizeof kept, hipMemcpyHostToDevice)); }
+  HIPCHK(hipMemset(dnb.p, 0, (size_t) n * 4));
+  VxParams p; memset(&p, 0, sizeof p);
+  p.bit_depth = 8; p.tools = (tools & VVCX_TOOL_DEPQUANT) | (ts_allowed ? VVCX_TOOL_TS : 0) | (mts_allowed ? VVCX_TOOL_MTS : 0);
+  hipLaunchKernelGGL(vvcx_leaf_rc_kernel, dim3((unsigned) n), dim3(VXD_NT), 0, 0, p, dctx.p, dlev.p, w, h, comp, mts_idx, form, dscan.p, dco.p, dout.p, dby.p, cap, dnb.p);
+  HIPCHK(hipGetLastError());
+  std::vector<unsigned long long> o((size_t) n * 2); std::vector<uint16_t> co((size_t) n * 2 * VXD_NUM_CTX); std::vector<uint32_t> nb((size_t) n);
+  HIPCHK(hipMemcpy(o.data(), dout.p, (size_t) n * 16, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(co.data(), dco.p, co.size() * 2, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(nb.data(), dnb.p, (size_t) n * 4, hipMemcpyDeviceToHost));
+  for (int i = 0; i < n; i++) {
+    frac_bits[i] = o[(size_t) i * 2]; rc_last[i] = (int32_t) (long long) o[(size_t) i * 2 + 1];
+    uint16_t *d0 = s0_out + (size_t) i * VX_NUM_CTX_REF, *d1 = s1_out + (size_t) i * VX_NUM_CTX_REF;
+    memcpy(d0, s0, VX_NUM_CTX_REF * 2); memcpy(d1, s1, VX_NUM_CTX_REF * 2);
+    ctx_to_reference_order(co.data() + (size_t) i * 2 * VXD_NUM_CTX, d0, d1);
+    if (form == 3) {
+      if (nb[(size_t) i] > cap) return fail(VVCX_ERR_ARG, "block %d wrote %u bytes, room for %u", i, nb[(size_t) i], cap);
+      nbytes[i] = (int32_t) nb[(size_t) i];
+    }
+  }
+  if (form == 3) HIPCHK(hipMemcpy(bytes, dby.p, (size_t) n * cap, hipMemcpyDeviceToHost));
+  return VVCX_OK;
+}
+
+// ≙ BinEncoder_Std (EL/BinEncoder.cpp:106-420) over an operation string from the I-slice contexts at qp: the device's arith_bin / arith_bins_ep / arith_trm / arith_finish
+extern "C" int vvcx_arith_encode(int qp, const int32_t *ops, int nops, uint8_t *out, int cap, int *nbytes, int device)
+{
+  if (!ops || !out || !nbytes || nops < 0 || cap <= 0) return fail(VVCX_ERR_ARG, "bad argument");
+  int kept_of[VX_NUM_CTX_REF];
+  for (int k = 0; k < VX_NUM_CTX_REF; k++) kept_of[k] = -1;
+  for (int k = 0; k < VXD_NUM_CTX; k++) kept_of[VX_CTX_REF_INDEX[k]] = k;
+  std::vector<int32_t> o((size_t) nops * 3 + 1);
+  for (int i = 0; i < nops; i++) {
+    const int kind = ops[3 * i], a = ops[3 * i + 1], b = ops[3 * i + 2];
+    int a2 = a;
+    if (kind == 0) { if (a < 0 || a >= VX_NUM_CTX_REF || kept_of[a] < 0 || (b != 0 && b != 1)) return fail(VVCX_ERR_ARG, "operation %d: context %d is not one the library keeps, or bin %d", i, a, b); a2 = kept_of[a]; }
+    else if (kind == 1) { if (b < 1 || b > 32 || (b < 32 && ((uint32_t) a >> b))) return fail(VVCX_ERR_ARG, "operation %d: %d bypass bins of value %u", i, b, (uint32_t) a); }
+    else if (kind != 2 || (a != 0 && a != 1)) return fail(VVCX_ERR_ARG, "operation %d: kind %d", i, kind);
+    o[(size_t) i * 3] = kind; o[(size_t) i * 3 + 1] = a2; o[(size_t) i * 3 + 2] = b;
+  }
+  uint16_t s0[VX_NUM_CTX_REF], s1[VX_NUM_CTX_REF], kept[2 * VXD_NUM_CTX];
+  vvcx_ctx_init(qp, s0, s1); ctx_from_reference_order(s0, s1, kept);
+  ON_DEVICE(device);
+  DevBuf<uint16_t> dctx; DevBuf<int32_t> dops; DevBuf<uint8_t> dby; DevBuf<uint32_t> dnb;
+  HIPCHK(dctx.alloc(2 * VXD_NUM_CTX)); HIPCHK(dops.alloc(o.size())); HIPCHK(dby.alloc((size_t) cap)); HIPCHK(dnb.alloc(1));
+  HIPCHK(hipMemcpy(dctx.p, kept, sizeof kept, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dops.p, o.data(), o.size() * 4, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(vvcx_leaf_arith_kernel, dim3(1), dim3(VXD_NT), 0, 0, dctx.p, dops.p, nops, dby.p, (uint32_t) cap, dnb.p);
+  HIPCHK(hipGetLastError());
+  uint32_t nb = 0;
+  HIPCHK(hipMemcpy(&nb, dnb.p, 4, hipMemcpyDeviceToHost));
+  if (nb > (uint32_t) cap) return fail(VVCX_ERR_ARG, "buffer too small: %u bytes needed", nb);
+  HIPCHK(hipMemcpy(out, dby.p, nb, hipMemcpyDeviceToHost));
+  *nbytes = (int) nb;
   return VVCX_OK;
 }
 

@@ -4775,6 +4775,70 @@ extern "C" __global__ void __launch_bounds__(NT, VXD_WPE) vvcx_leaf_scan_kernel(
   const ScanGeo g = scan_geo(w, h);
   for (int sp = VTX; sp < g.nscan; sp += NT) idx[sp] = (uint16_t) scan_blk(g, sp);
 }
+// residual coding of one block of levels per workgroup from given context models, in each of the forms the path has (tests/golden/residual_range.npz): form 0 the single-lane
+// estimator (residual_coding / rc_ts_serial), 1 / 2 the wave estimator on levels in the wave's LDS slot / in HBM, 3 the writer on a coder of its own: the TU's transform
+// indices as walk_tree writes them, the levels, the terminating bin, finish.  p carries the tool bits that steer the syntax; out = {bits, rc_last} per block, ctx_out the
+// end states, bytes / nbytes the writer's payload (cap bytes per block)
+extern "C" __global__ void __launch_bounds__(NT, VXD_WPE) vvcx_leaf_rc_kernel(VxParams p, const uint16_t *ctx, const int16_t *lev, int w, int h, int ch, int mts, int form, uint16_t *scan,
+                                                                              uint16_t *ctx_out, unsigned long long *out, uint8_t *bytes, uint32_t cap, uint32_t *nbytes)
+{
+  if (VTX == 0) L.par = p;
+  load_tables();
+  for (int i = VTX; i < NCTX; i += NT) { L.ctxs[CI_CUR].s0[i] = ctx[i]; L.ctxs[CI_CUR].s1[i] = ctx[NCTX + i]; }
+  __syncthreads();
+  const int wave = uni(VTX >> 6), lane = VTX & 63, P = w * h;
+  const int16_t *lv = lev + (size_t) blockIdx.x * P;
+  if (wave == 0) {
+    Cab cb; cb.ci = CI_CUR; cb.bits = 0;
+    int last = -1;
+    if (form == 1 || form == 2) {
+      if (form == 1) {
+        for (int i = lane; i < P; i += 64) L.wm[0].slot[BUF + i] = lv[i];
+        wave_sync();
+        residual_coding_wave<true>(cb, 0, nullptr, w, h, ch, lane, mts > 1);
+      } else residual_coding_wave<false>(cb, 0, lv, w, h, ch, lane, mts > 1);
+      wave_sync();
+      last = L.rc_last[0];
+    } else if (lane == 0) {
+      uint16_t *sc = scan + (size_t) blockIdx.x * 1024;
+      if (form == 0) {
+        if (mts == 1) rc_ts_serial(cb, lv, w, h); else { residual_coding(cb, lv, w, h, ch, sc, mts > 1); last = L.rc_last[0]; }
+      } else {
+        L.aw_out = bytes + (size_t) blockIdx.x * cap; L.aw_cap = cap;
+        arith_start();
+        if (!ch) enc_tu_mts<true>(cb, w, h, mts);
+        if (mts == 1) rc_ts_serial<true>(cb, lv, w, h); else { residual_coding<true>(cb, lv, w, h, ch, sc, mts > 1); last = L.rc_last[0]; }
+        arith_trm(1); arith_finish();
+        nbytes[blockIdx.x] = L.aw.n;
+      }
+    }
+    if (lane == 0) { out[blockIdx.x * 2] = cb.bits; out[blockIdx.x * 2 + 1] = (unsigned long long) (long long) last; }
+  }
+  __syncthreads();
+  uint16_t *co = ctx_out + (size_t) blockIdx.x * 2 * NCTX;
+  for (int i = VTX; i < NCTX; i += NT) { co[i] = L.ctxs[CI_CUR].s0[i]; co[NCTX + i] = L.ctxs[CI_CUR].s1[i]; }
+}
+// the arithmetic coder over an operation string (tests/golden/arith_range.npz): ops[i] = {kind, a, b}: 0 = bin b on context a (the kept models' index), 1 = b bypass bins of
+// value a, 2 = terminating bin a; then finish
+extern "C" __global__ void __launch_bounds__(NT, VXD_WPE) vvcx_leaf_arith_kernel(const uint16_t *ctx, const int32_t *ops, int nops, uint8_t *bytes, uint32_t cap, uint32_t *nbytes)
+{
+  load_tables();
+  for (int i = VTX; i < NCTX; i += NT) { L.ctxs[CI_CUR].s0[i] = ctx[i]; L.ctxs[CI_CUR].s1[i] = ctx[NCTX + i]; }
+  __syncthreads();
+  if (VTX == 0) {
+    Cab cb; cb.ci = CI_CUR; cb.bits = 0;
+    L.aw_out = bytes; L.aw_cap = cap;
+    arith_start();
+    for (int i = 0; i < nops; i++) {
+      const int kind = ops[3 * i], a = ops[3 * i + 1], b = ops[3 * i + 2];
+      if (kind == 0) enc_bin<true>(cb, (unsigned) b, a);
+      else if (kind == 1) enc_ep<true>(cb, (uint32_t) a, b);
+      else arith_trm((unsigned) a);
+    }
+    arith_finish();
+    nbytes[0] = L.aw.n;
+  }
+}
 
 // forest inference on its own: one thread per feature row, trees in order (the sum order of OP_FAST and of sklearn's predict_proba)
 extern "C" __global__ void __launch_bounds__(NT, VXD_WPE) vvcx_leaf_forest_kernel(VxParams p, const int32_t *rows, int n, int32_t *out)

@@ -671,3 +671,29 @@ def lfnst_depquant_batch(org, pred, w, h, bit_depth, qp, comp, lfnst_idx, intra_
     _chk(L, L.vvcx_lfnst_depquant_batch(org.ctypes.data, pred.ctypes.data, w, h, bit_depth, qp, comp, lfnst_idx, intra_dir, cbf_cb, lam, s0.ctypes.data, s1.ctypes.data, n,
                                         lev.ctypes.data, rec.ctypes.data, sse.ctypes.data, cbf.ctypes.data, device))
     return lev.reshape(n, h, w), rec.reshape(n, h, w), sse, cbf
+
+
+def residual_coding_batch(lev, w, h, comp, tools, ts_allowed, mts_allowed, mts_idx, s0, s1, form, device=0, lib_path=None):
+    """vvcx_residual_coding_batch: n blocks of levels back to back, each from the states s0 / s1, in one of the path's forms (0 single-lane estimator, 1 / 2 wave estimator
+    from LDS / device memory, 3 writer) -> (bits uint64 [n], s0' [n, 386], s1' [n, 386], rc_last int32 [n], list of n byte strings (form 3) or None)"""
+    L = load_library(lib_path)
+    lev = np.ascontiguousarray(lev, np.int16).ravel()
+    s0 = np.ascontiguousarray(s0, np.uint16); s1 = np.ascontiguousarray(s1, np.uint16)
+    n = lev.size // (w * h)
+    bits = np.zeros(n, np.uint64); e0 = np.zeros((n, 386), np.uint16); e1 = np.zeros((n, 386), np.uint16); last = np.zeros(n, np.int32)
+    cap = 6 * w * h + 64 if form == 3 else 0
+    by = np.zeros(max(1, n * cap), np.uint8); nb = np.zeros(n, np.int32)
+    L.vvcx_residual_coding_batch.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_uint32] + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p, C.c_int]
+    _chk(L, L.vvcx_residual_coding_batch(lev.ctypes.data, w, h, n, comp, tools, int(ts_allowed), int(mts_allowed), mts_idx, s0.ctypes.data, s1.ctypes.data, form, bits.ctypes.data,
+                                         e0.ctypes.data, e1.ctypes.data, last.ctypes.data, by.ctypes.data if form == 3 else None, cap, nb.ctypes.data if form == 3 else None, device))
+    return bits, e0, e1, last, ([by[i * cap:i * cap + nb[i]].copy() for i in range(n)] if form == 3 else None)
+
+
+def arith_encode(qp, ops, device=0, lib_path=None):
+    """vvcx_arith_encode: rows of {kind, a, b} (0 context bin b on model a, 1 b bypass bins of value a, 2 terminating bin a) from the I-slice contexts at qp -> the bytes"""
+    L = load_library(lib_path)
+    ops = np.ascontiguousarray(ops, np.int32).reshape(-1, 3)
+    out = np.zeros(len(ops) * 4 + 64, np.uint8); nb = C.c_int(0)
+    L.vvcx_arith_encode.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    _chk(L, L.vvcx_arith_encode(int(qp), ops.ctypes.data, len(ops), out.ctypes.data, len(out), C.byref(nb), device))
+    return out[:nb.value].copy()

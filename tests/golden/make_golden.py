@@ -1655,8 +1655,350 @@ def gen_cclm_shapes():
     _report("cclm_shapes.npz", len(meta))
 
 
+# ---- residual coding, the arithmetic coder and the bin model at their range edges (residual_range / arith_range / cabac_range) ----
+RC_ISP_SHAPES = [s for n in (8, 16, 32, 64) for s in ((1, n), (2, n), (n, 1), (n, 2)) if s[0] * s[1] >= 16]
+MIN_IN_GROUP = (0, 1, 2, 3, 4, 6, 8, 12, 16, 24)      # first position of each last_sig_coeff prefix group
+
+
+def _ref_states(qp):
+    n = R.ref_ctx_count()
+    s0 = np.zeros(n, np.uint16); s1 = np.zeros(n, np.uint16); rate = np.zeros(n, np.uint8)
+    R.ref_ctx_init(int(qp), 2, P(s0), P(s1), P(rate))
+    return s0, s1, rate
+
+
+def _orc_residual(L, s0, s1, lev, m, write):
+    """oracle: one TU from the states s0 / s1 -> (bits, end s0, end s1, last, bytes)"""
+    w, h = int(m["w"]), int(m["h"])
+    bits = C.c_uint64(); e0 = np.zeros(386, np.uint16); e1 = np.zeros(386, np.uint16); last = C.c_int(); out = np.zeros(6 * w * h + 64, np.uint8)
+    lev = np.ascontiguousarray(lev, np.int16)
+    n = L.orc_residual_leaf(P(s0), P(s1), P(lev), w, h, int(m["comp"]), int(m["dq"]), int(m["ts"]), int(m["mts"]), int(m["mi"]), int(write), C.byref(bits), P(e0), P(e1), C.byref(last),
+                            P(out), len(out))
+    assert n >= 0
+    return bits.value, e0, e1, last.value, out[:n].copy()
+
+
+def _rem_thresholds(rice, top):
+    """the coded remainders at which the code of encodeRemAbsEP changes shape for a Rice parameter: the last short code and the first escape, both sides of every step of the
+    prefix length, code 4094 / 4095 on either side of the longest prefix; at most top"""
+    v = {0, 1, (5 << rice) - 1, 5 << rice}
+    for p in range(12):
+        for code in ((2 << p) - 2, (2 << p) - 1):
+            v.add((code + 5) << rice); v.add(((code + 5) << rice) | ((1 << rice) - 1))
+    for code in (4094, 4095):
+        v.add((code + 5) << rice); v.add(((code + 5) << rice) | ((1 << rice) - 1))
+    return sorted(x for x in v if x <= top)
+
+
+def residual_range_meta(chain):
+    """the meta rows (oracle_lib.RC_META) of residual_range.npz; chain: the side of the block the search for many models in one run of 64 positions found (its levels are stored)"""
+    O = _olib()
+    rows = []
+    add = lambda comp, w, h, dq, ts, mts, mi, isp, start, pat, p0=0, p1=0, p2=0, seed=0: rows.append((comp, w, h, dq, ts, mts, mi, isp, start, pat, p0, p1, p2, seed))
+    shapes = [(0, w, h, 0) for (w, h) in LEAF_LUMA_SHAPES] + [(1, w // 2, h // 2, 0) for (w, h) in LEAF_CHROMA_SHAPES] + [(0, w, h, 1) for (w, h) in RC_ISP_SHAPES]
+    assert len(shapes) == 25 + 19 + 14
+    for si, (comp, w, h, isp) in enumerate(shapes):                  # every shape residual coding can be handed, dep-quant off and on
+        allowed = int(comp == 0 and not isp and w <= 32 and h <= 32)
+        zw, zh = min(w, 32), min(h, 32)
+        for dq in (0, 1):
+            st = (si + 3 * dq) % 6
+            base = (comp, w, h, dq, allowed, allowed, 0, isp, st)
+            for (x, y) in sorted({(0, 0), (zw - 1, 0), (0, zh - 1), (zw - 1, zh - 1)}):      # one coefficient at each corner of the coded area
+                add(*base, O.RC_SINGLE, x, y, (1, -2, 3, -32768)[(x > 0) + 2 * (y > 0)])
+            add(*base, O.RC_ONES, 0, seed=1000 + si); add(*base, O.RC_ONES, 1, seed=2000 + si)
+            for k in ((0, 2) if (si + dq) & 1 else (1,)):
+                add(*base, O.RC_MAX, k)
+            for k in range(3):
+                add(*base, O.RC_NOISE, k, seed=3000 + 10 * si + k)
+    # every last_sig_coeff group boundary of X and Y (both outcomes of gx < maxX): sides that code 32 of 64 and 16 of a 32-point MTS side among them
+    for (comp, w, h, mi) in ((0, 32, 32, 0), (0, 64, 64, 0), (0, 16, 4, 0), (0, 4, 32, 0), (0, 8, 8, 0), (1, 32, 32, 0), (1, 4, 16, 0), (1, 8, 2, 0), (0, 32, 32, 2), (0, 32, 8, 3), (0, 16, 32, 4), (0, 32, 16, 5), (0, 1, 32, 0),
+                             (0, 64, 2, 0)):
+        isp = int(w < 4 or h < 4) if comp == 0 else 0
+        allowed = int(comp == 0 and not isp and w <= 32 and h <= 32)
+        zw, zh = O._rc_coded_area(w, h, mi)
+        edge = lambda n: sorted({p for g0 in MIN_IN_GROUP if g0 < n for p in (g0, min(n, ([q for q in MIN_IN_GROUP if q > g0] + [n])[0]) - 1)})
+        for dq in (0, 1):
+            for x in edge(zw):
+                add(comp, w, h, dq, allowed, allowed, mi, isp, 1, O.RC_SINGLE, x, 0, 2)
+            for y in edge(zh):
+                add(comp, w, h, dq, allowed, allowed, mi, isp, 4, O.RC_SINGLE, 0, y, -1)
+            add(comp, w, h, dq, allowed, allowed, mi, isp, 2, O.RC_SINGLE, zw - 1, zh - 1, 5)
+            if mi > 1:                                              # the same sides with levels all over the coded area: the groups of the zeroed area are skipped
+                add(comp, w, h, dq, allowed, allowed, mi, isp, 3, O.RC_NOISE, 2, seed=3900 + mi); add(comp, w, h, dq, allowed, allowed, mi, isp, 5, O.RC_MAX, 2)
+    # the remainder code at every threshold for each Rice parameter, behind context-coded bins and in the bypass pass; neighbour levels (20 / 27 / 34 / 48 behind
+    # context-coded bins, where 5 * 4 is taken off the template sum; 0 / 7 / 14 / 28 in the bypass pass) put the template sum into each class of g_auiGoRiceParsCoeff
+    for (comp, w, h, isp) in ((0, 4, 4, 0), (1, 4, 4, 0), (0, 1, 16, 1)):
+        allowed = int(comp == 0 and not isp)
+        for dq in (0, 1):
+            for rice, nb in enumerate((20, 27, 34, 48)):
+                for b in _rem_thresholds(rice, (32768 - 4) >> 1):
+                    for a in (2 * b + 4, 2 * b + 5):
+                        if a <= 32768:
+                            add(comp, w, h, dq, allowed, allowed, 0, isp, 2 * dq + (rice & 1), O.RC_REM_CTX, a, nb, int(a == 32768 or (b & 1)))
+    for (comp, w, h) in ((0, 8, 8), (1, 8, 8), (0, 16, 8)):
+        for dq in (0, 1):
+            for rice, nb in enumerate((0, 7, 14, 28)):
+                for b in _rem_thresholds(rice, 32768):
+                    if b > 8:
+                        add(comp, w, h, dq, int(comp == 0), int(comp == 0), 0, 0, 3 + dq, O.RC_REM_BYP, b, nb, 4 * int(b == 32768 or (b & 1)))
+                for v in range(4 if dq else 1):                     # above, at and below the zero position for each quantiser state (odd levels coded before set the state)
+                    for a in range(0, 9):
+                        add(comp, w, h, dq, int(comp == 0), int(comp == 0), 0, 0, v, O.RC_REM_BYP, a, nb, v)
+    # coefficient groups: empty ones, groups whose only level sits where the significance is inferred, groups with a significant right / lower neighbour only
+    for (comp, w, h) in ((0, 16, 16), (1, 16, 16), (0, 16, 8), (1, 8, 16)):
+        ng = (w // 4) * (h // 4); gw = w // 4
+        masks = [1 | 1 << (ng - 1), (1 << ng) - 1, 1 | 1 << (gw - 1), 1 | 1 << (ng - gw), 1 | 1 << (ng - 1) | 1 << (ng - 2), 1 | 1 << (ng - 1) | 1 << (ng - 1 - gw), 0x5A5A & ((1 << ng) - 1) | 1 << (ng - 1),
+                 0xA5A5 & ((1 << ng) - 1), 1 << (ng - 1), 1 << 1 | 1 << (ng - 1), 1 << gw | 1 << (ng - 1)]
+        for dq in (0, 1):
+            for k, mk in enumerate(masks):
+                for full in (0, 1):
+                    add(comp, w, h, dq, int(comp == 0), int(comp == 0), 0, 0, (k + dq) % 6, O.RC_GROUPS, mk, full, seed=5000 + k)
+    # transform skip: the same extremes on every shape it is allowed for, and the remainder thresholds (levels of 10 and more) for each of its Rice parameters
+    for si, (w, h) in enumerate((w, h) for w in (4, 8, 16, 32) for h in (4, 8, 16, 32)):
+        for mts in ((si & 1),):
+            base = (0, w, h, 1, 1, mts, 1, 0, si % 6)
+            add(*base, O.RC_ONES, 0, seed=6000 + si); add(*base, O.RC_ONES, 1, seed=6100 + si)
+            for k in range(3):
+                add(*base, O.RC_MAX, k); add(*base, O.RC_NOISE, k, seed=6200 + 10 * si + k)
+            add(*base, O.RC_SINGLE, w - 1, h - 1, -32768); add(*base, O.RC_SINGLE, 0, 0, 1)
+    for (w, h) in ((4, 4), (8, 4)):
+        for rice, nb in enumerate((0, 12, 25)):
+            for b in _rem_thresholds(rice, (32768 - 10) >> 1):
+                for a in (2 * b + 10, 2 * b + 11):
+                    if a <= 32768:
+                        add(0, w, h, 1, 1, 1, 1, 0, rice, O.RC_TS_THR, a, nb, int(a == 32768 or (b & 1)))
+        for nb in (3, -7, 40):                                      # levels below, at and above the neighbour's (deriveModCoeff)
+            for a in range(1, 12):
+                add(0, w, h, 1, 1, 0, 1, 0, 5, O.RC_TS_THR, a, nb, a & 1)
+    add(0, chain, chain, 1, 1, 1, 0, 0, 1, O.RC_CHAIN)
+    return np.array(rows, np.int32)
+
+
+def gen_residual_range():
+    O = _olib(); L = O.lib()
+    L.orc_residual_leaf.argtypes = [C.c_void_p] * 3 + [C.c_int] * 8 + [C.c_void_p] * 5 + [C.c_int]
+    R.ref_residual_decode.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 4
+    env = R.ref_env_create(128, 128, 8)
+    cnt = np.zeros(O.RC_COUNTERS, np.int64)
+    row = lambda m: dict(zip(O.RC_META, (int(v) for v in m)))
+    # start states: the I-slice contexts of the REFERENCE at slice QP 4, 27 and 51; and what a dense luma block with both transform indices, a dense transform-skip block and a dense
+    # chroma block leave of each (all of these cases' model sets away from their initial values)
+    starts = []
+    for qp in (4, 27, 51):
+        s0, s1, _ = _ref_states(qp)
+        starts.append((s0, s1))
+    for k in range(3):
+        s0, s1 = starts[k]
+        for j, (comp, w, h, mi) in enumerate(((0, 16, 16, 0), (0, 8, 8, 1), (1, 8, 8, 0), (0, 16, 16, 3))):
+            m = dict(comp=comp, w=w, h=h, dq=1, ts=int(comp == 0), mts=int(comp == 0), mi=mi)
+            lev = O.residual_range_levels((comp, w, h, 1, m["ts"], m["mts"], mi, 0, 0, O.RC_NOISE, 2, 0, 0, 7000 + 10 * k + j))
+            _, s0, s1, _, _ = _orc_residual(L, s0, s1, lev, m, 1)
+        starts.append((s0, s1))
+    starts = np.array(starts, np.uint16)                            # [6][2][386]
+    # rc_chain groups at most 64 distinct models per round: the block, among seeded 8x8 and 16x16 luma blocks with dep-quant on, that uses the most models in one run of 64 positions
+    # (random blocks reach about 60; from the best of them, single levels are changed for as long as the count does not fall)
+    L.orc_residual_counters(P(cnt))
+    cg = np.random.default_rng(8000)
+    def models(lev, cw):
+        _orc_residual(L, starts[1][0], starts[1][1], lev, dict(comp=0, w=cw, h=cw, dq=1, ts=1, mts=1, mi=0), 0)
+        L.orc_residual_counters(P(cnt))
+        return int(cnt[O.RC_MAX_MODELS_IN_64])
+    best = (0, None)
+    for cw in (8, 16):
+        for restart in range(4):
+            lev = (cg.integers(0, 6, (cw, cw)) * (cg.random((cw, cw)) < 0.5) * np.where(cg.random((cw, cw)) < 0.5, -1, 1)).astype(np.int16); lev[cw - 1, cw - 1] = 1
+            sc = models(lev, cw)
+            for it in range(6000):
+                cand = lev.copy()
+                for k in range(int(cg.integers(1, 3))):
+                    cand[int(cg.integers(0, cw)), int(cg.integers(0, cw))] = int(cg.integers(-5, 6))
+                if cand.any():
+                    c2 = models(cand, cw)
+                    if c2 >= sc:
+                        lev, sc = cand, c2
+            if sc > best[0]:
+                best = (sc, lev.copy())
+    print("most context models in one run of 64 scan positions:", best[0], best[1].shape)
+    chain_lev = best[1]
+    meta = residual_range_meta(chain_lev.shape[0])
+    assert len(set(map(tuple, meta.tolist()))) == len(meta)
+    tot = np.zeros(O.RC_COUNTERS, np.int64)
+    bits_all, last_all, wbits_all, moved, wmoved, moved_off, wmoved_off, byts, byte_off = [], [], [], [], [], [0], [0], [], [0]
+    mts_ctx = C.c_int(); mts0 = R.ref_ctx_set(b"MTSIndex", 0, C.byref(mts_ctx)); mts_models = set(range(mts0, mts0 + mts_ctx.value))
+    for i, mrow in enumerate(meta):
+        m = row(mrow)
+        lev = O.residual_range_levels(mrow, chain_lev)
+        s0, s1 = starts[m["start"]]
+        L.orc_residual_counters(P(cnt))
+        bits, e0, e1, last, _ = _orc_residual(L, s0, s1, lev, m, 0)
+        L.orc_residual_counters(P(cnt)); tot[:O.RC_MAX_MODELS_IN_64] += cnt[:O.RC_MAX_MODELS_IN_64]; tot[O.RC_MAX_MODELS_IN_64] = max(tot[O.RC_MAX_MODELS_IN_64], cnt[O.RC_MAX_MODELS_IN_64])
+        wbits, w0, w1, wlast, by = _orc_residual(L, s0, s1, lev, m, 1)
+        assert wlast == last
+        # the REFERENCE's reader on the oracle's bytes: the levels come back, the stream is consumed exactly, its end states are the oracle's
+        rl = np.zeros(m["w"] * m["h"], np.int32); rmi = C.c_int(-1); r0 = np.zeros(386, np.uint16); r1 = np.zeros(386, np.uint16)
+        rc = R.ref_residual_decode(env, m["comp"], m["w"], m["h"], m["isp"], m["dq"], m["ts"], m["mts"], P(s0), P(s1), P(by), len(by), P(rl), C.byref(rmi), P(r0), P(r1))
+        assert rc == 0, ("reader", rc, m)
+        assert np.array_equal(rl, lev.ravel().astype(np.int32)), ("levels", m)
+        assert rmi.value == m["mi"], ("mtsIdx", rmi.value, m)
+        assert np.array_equal(r0, w0) and np.array_equal(r1, w1), ("end states", m)
+        # the levels alone: the same models but those of the transform indices, which stay where they started
+        diff = set(np.flatnonzero((e0 != w0) | (e1 != w1)).tolist())
+        assert diff <= mts_models and all(e0[k] == s0[k] and e1[k] == s1[k] for k in mts_models), m
+        bits_all.append(bits); last_all.append(last); wbits_all.append(wbits)
+        a = O.sparse_states(s0, s1, e0, e1); b = O.sparse_states(s0, s1, w0, w1)
+        moved.append(a); wmoved.append(b); moved_off.append(moved_off[-1] + len(a)); wmoved_off.append(wmoved_off[-1] + len(b))
+        byts.append(by); byte_off.append(byte_off[-1] + len(by))
+    print("residual counters", tot.tolist())
+    O.residual_counter_conditions(tot, best[0])
+    np.savez_compressed(os.path.join(HERE, "residual_range.npz"), meta=meta, starts=starts, bits=np.array(bits_all, np.uint64), last=np.array(last_all, np.int32),
+                        wbits=np.array(wbits_all, np.uint64), moved=np.concatenate(moved), moved_off=np.array(moved_off, np.int64), wmoved=np.concatenate(wmoved),
+                        wmoved_off=np.array(wmoved_off, np.int64), bytes=np.concatenate(byts), byte_off=np.array(byte_off, np.int64), chain_max=np.array([best[0]], np.int64), chain_lev=chain_lev)
+    _report("residual_range.npz", len(meta))
+
+
+def _ep_ops(bits, chunk=32):
+    """bypass operations {1, value, count} for a list of bins, at most chunk (<= 32) per operation"""
+    ops = []
+    for i in range(0, len(bits), chunk):
+        v = 0
+        for b in bits[i:i + chunk]:
+            v = (v << 1) | int(b)
+        ops.append((1, v - (1 << 32) if v >= (1 << 31) else v, len(bits[i:i + chunk])))
+    return ops
+
+
+def _range_after(qp, ops):
+    """the coder's range after context-coded and terminating operations from the I-slice contexts at qp (a mirror of TBinEncoder::encodeBin's range arithmetic on the REFERENCE's
+    initial states and rates; bypass bins leave the range alone): what the constructed bypass strings divide by"""
+    s0, s1, rate = _ref_states(qp)
+    s0 = s0.astype(np.int64); s1 = s1.astype(np.int64)
+    renorm = [6, 5, 4, 4, 3, 3, 3, 3] + [2] * 8 + [1] * 16
+    rg = 510
+    for (kind, a, b) in ops:
+        if kind == 0:
+            q = ((s0[a] + s1[a]) >> 8) & 0xff; mps = q >> 7
+            if q & 0x80:
+                q ^= 0xff
+            lps = (((q >> 2) * (rg >> 5)) >> 1) + 4
+            rg -= lps
+            if b != mps:
+                rg = lps << renorm[lps >> 3]
+            elif rg < 256:
+                rg <<= 1
+            r0 = 2 + ((int(rate[a]) >> 2) & 3); r1 = 3 + r0 + (int(rate[a]) & 3)
+            s0[a] -= (s0[a] >> r0) & 0x7FE0; s1[a] -= (s1[a] >> r1) & 0x7FFE
+            if b:
+                s0[a] += (0x7fff >> r0) & 0x7FE0; s1[a] += (0x7fff >> r1) & 0x7FFE
+        elif kind == 2:
+            rg -= 2
+            if a:
+                rg = 256
+            elif rg < 256:
+                rg <<= 1
+    return int(rg)
+
+
+def gen_arith_range():
+    """operation strings for the arithmetic coder, constructed: see the comments; bytes from the REFERENCE's BinEncoder_Std"""
+    O = _olib(); L = O.lib()
+    sz = C.c_int()
+    ctx_of = lambda name, idx, k: R.ref_ctx_set(name, idx, C.byref(sz)) + k
+    sig, gtx, lastx, grp, mts = ctx_of(b"SigFlag", 0, 3), ctx_of(b"GtxFlag", 1, 2), ctx_of(b"LastX", 0, 1), ctx_of(b"SigCoeffGroup", 0, 0), ctx_of(b"MTSIndex", 0, 0)
+    cases = []                                                       # (qp, ops)
+    # carry chains.  In bypass mode the range r is constant and n bins with the value B leave low = r * B behind whatever was there.  With B = floor((2^m - 1) / r), r * B is
+    # m one-bits less a remainder below r, which the last nine of them take up without a borrow: m = 8 * run + 9 puts `run` bytes of 0xff into the stream, which the coder
+    # has to keep back.  Zeros behind them resolve the run without a carry, ones with one; a few ones and the end of the string leave the carry to finish(), a string that ends
+    # at once or on zeros ends it there without one.  pad zeros in front move the run through the eight alignments; context-coded bins in front give another range.
+    for qp, prefix in ((27, []), (4, [(0, sig, 1), (0, sig, 0), (0, gtx, 1), (0, lastx, 1), (0, sig, 1)]), (51, [(0, grp, 0)] * 7 + [(0, mts, 1)] * 3 + [(2, 0, 0)])):
+        r = _range_after(qp, prefix)
+        for run in (3, 8, 40):
+            m = 8 * run + 9
+            B = ((1 << m) - 1) // r
+            for pad in range(8):
+                bits = [0] * pad + [int(ch) for ch in bin(B)[2:].zfill(m)]
+                tails = [[], [0] * 32, [1] * 32] + [[1] * t for t in (1, 2, 3, 5, 9)] + [[0] * t for t in (1, 3)] + [[1, 0], [0, 1, 1, 1], [1] * 12 + [0] * 20]
+                for tail in (tails if run == 3 or pad in (0, 5) else tails[:5]):
+                    cases.append((qp, prefix + _ep_ops(bits + tail, 32 if (pad + len(tail)) & 1 else 13)))
+    # bypass runs of every length 1..32: all ones, a random value, one bin set
+    g = np.random.default_rng(9100)
+    for n in range(1, 33):
+        ops = []
+        for v in ((1 << n) - 1, int(g.integers(0, 1 << n)), 1 << (n - 1), 0, int(g.integers(0, 1 << n))):
+            ops.append((1, v - (1 << 32) if v >= (1 << 31) else v, n))
+        cases.append((27, ops)); cases.append((51, [(0, sig, 1), (0, gtx, 0)] + ops + [(2, 1, 0)]))
+    # terminating bins of 0 with the range above and below 256 after the subtraction: bin strings on one model searched for a range of 256 / 257 and of 258 / 259 in front of them
+    found = {}
+    for seed in range(4000):
+        gg = np.random.default_rng(9200 + seed)
+        pre = [(0, int(gg.choice([sig, gtx, lastx])), int(gg.integers(0, 2))) for _ in range(int(gg.integers(1, 12)))]
+        r = _range_after(27, pre)
+        if r in (256, 257, 258, 259, 510, 300) and r not in found:
+            found[r] = pre
+    assert {256, 257, 258, 259} <= set(found), sorted(found)
+    for r, pre in sorted(found.items()):
+        cases.append((27, pre + [(2, 0, 0), (1, 0x155, 9), (2, 0, 0), (0, sig, 1), (2, 0, 0), (2, 1, 0)]))
+    # context-coded bins at the least and the greatest LPS range: a model saturated by 300 equal bins (LPS range 4: the other bin costs six shifts), then the other way, then bins
+    # that alternate and bring it to the middle, where the LPS range is greatest (at a range of 480 and more, right behind a terminating bin of 1 ... of 0)
+    for qp in (4, 51):
+        for c in (sig, gtx, lastx, grp, mts):
+            cases.append((qp, [(0, c, 0)] * 300 + [(0, c, 1)] + [(0, c, 1)] * 300 + [(0, c, 0)] + [(0, c, k & 1) for k in range(64)] + [(2, 0, 0), (0, c, 0), (0, c, 1), (2, 1, 0)]))
+    cnt = np.zeros(8, np.int64); tot = np.zeros((4, 2), np.int64)
+    meta, ops_all, bytes_all = [], [], []
+    for qp, ops in cases:
+        a = np.array(ops, np.int64).astype(np.int32).reshape(-1, 3)
+        out = np.zeros(len(a) * 4 + 64, np.uint8); out2 = np.zeros_like(out)
+        n = R.ref_arith_encode(int(qp), P(a), len(a), P(out), len(out))
+        assert n > 0
+        L.orc_arith_counters(P(cnt))
+        assert L.orc_arith_encode(int(qp), P(a), len(a), P(out2), len(out2)) == n and np.array_equal(out[:n], out2[:n]), ("oracle", qp, ops[:8])
+        L.orc_arith_counters(P(cnt)); c2 = cnt.reshape(4, 2); tot[:, 0] += c2[:, 0]; tot[:, 1] = np.maximum(tot[:, 1], c2[:, 1])
+        meta.append((qp, len(a), n)); ops_all.append(a.ravel()); bytes_all.append(out[:n].copy())
+    print("arith counters {times, longest run}: writeOut plain, writeOut carry, finish carry, finish plain:", tot.tolist())
+    O.arith_counter_conditions(tot)
+    np.savez_compressed(os.path.join(HERE, "arith_range.npz"), meta=np.array(meta, np.int32), ops=np.concatenate(ops_all), bytes=np.concatenate(bytes_all))
+    _report("arith_range.npz", len(meta))
+
+
+def gen_cabac_range():
+    O = _olib()
+    n = R.ref_ctx_count()
+    qps = np.arange(-12, 71)
+    s0 = np.zeros((len(qps), n), np.uint16); s1 = np.zeros((len(qps), n), np.uint16); rate = np.zeros((len(qps), n), np.uint8)
+    for i, qp in enumerate(qps):
+        R.ref_ctx_init(int(qp), 2, P(s0[i]), P(s1[i]), P(rate[i]))
+    assert np.array_equal(s0[0], s0[12]) and np.array_equal(s0[-1], s0[12 + 63]) and (rate == rate[0]).all()      # the reference clips the QP to 0..63
+    # one model of every distinct adaptation rate of the rate table, from the least and the greatest state an initialisation can give (1 and 127, times 256) and from its own
+    # initial states at QP 0 and 63
+    seq = []
+    for rt in sorted(set(rate[0].tolist())):
+        ctx = int(np.flatnonzero(rate[0] == rt)[0])
+        for (a0, b0) in ((256 & 0x7FE0, 256 & 0x7FFE), ((127 << 8) & 0x7FE0, (127 << 8) & 0x7FFE), (int(s0[12, ctx]), int(s1[12, ctx])), (int(s0[75, ctx]), int(s1[75, ctx]))):
+            for kind in range(5):
+                bins = O.cabac_range_bins(kind)
+                a = np.array([a0], np.uint16); b = np.array([b0], np.uint16)
+                bits = R.ref_ctx_code_bins(P(a), P(b), int(rt), P(bins), len(bins))
+                seq.append((ctx, rt, a0, b0, kind, bits, int(a[0]), int(b[0])))
+    # calcRdCost at the lambdas of slice QP -12, 0, 32 and 63, with and without the dep-quant factor, on operands up to 2^62 (a CTU's SSE alone is about 2^34)
+    g = np.random.default_rng(9300)
+    edge = [0, 1, 1 << 32, 1 << 40, (1 << 53) - 1, (1 << 53) + 1, 1 << 62]
+    lam, fb, dist, cost = [], [], [], []
+    for qp in (-12, 0, 32, 63):
+        for f in (1.0, 2.0 ** (0.25 / 3)):
+            lm = float(0.57 * 2.0 ** ((qp - 12) / 3.0) * f)
+            pairs = [(a, b) for a in edge for b in edge] + [(int(g.integers(0, 1 << 40)), int(g.integers(0, 1 << 40))) for _ in range(16)]
+            for (a, b) in pairs:
+                sq = C.c_double()
+                lam.append(lm); fb.append(a); dist.append(b); cost.append(R.ref_calc_rd_cost(lm, 8, a, b, C.byref(sq)))
+    np.savez_compressed(os.path.join(HERE, "cabac_range.npz"), qps=qps.astype(np.int32), s0=s0, s1=s1, seq=np.array(seq, np.int64), lam=np.array(lam, np.float64),
+                        frac_bits=np.array(fb, np.uint64), dist=np.array(dist, np.uint64), cost=np.array(cost, np.float64))
+    print("rates", sorted(set(rate[0].tolist())), "sequences", len(seq), "rd rows", len(lam))
+    _report("cabac_range.npz", len(seq))
+
+
 if __name__ == "__main__":
     import sys
+    if len(sys.argv) > 1 and sys.argv[1] in ("residual_range", "arith_range", "cabac_range"):
+        globals()["gen_" + sys.argv[1]](); sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "cclm_shapes":
         gen_cclm_shapes(); sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "mip_range":
@@ -1724,5 +2066,5 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "cclm":
         gen_cclm(); sys.exit(0)      # added later: leaves the earlier fixtures (and the shared rng stream they used) untouched
     gen_transforms(); gen_dist(); gen_cabac(); gen_scan(); gen_intra(); gen_partition(); gen_trquant(); gen_bitstream(); gen_cclm(); gen_bitstream_cclm(); gen_trquant_mts(); gen_bitstream_mts(); gen_bitstream_mip(); gen_chroma_qp(); gen_deblock(); gen_mip(); gen_depquant(); gen_bitstream_dq(); gen_lfnst(); gen_bitstream_lfnst(); gen_bitstream_jccr(); gen_ict(); gen_decision_helpers(); gen_ts(); gen_bitstream_ts(); gen_isp(); gen_bitstream_isp(); gen_lmcs(); gen_bitstream_wpp(); gen_lmcs_analysis(); gen_sao(); gen_alf(); gen_trquant_range()
-    gen_intra_shapes(); gen_cclm_shapes(); gen_mip_range(); gen_dist_range(); gen_deblock_range(); gen_sao_range(); gen_alf_range()      # seeds of their own: the order does not matter
+    gen_intra_shapes(); gen_cclm_shapes(); gen_mip_range(); gen_dist_range(); gen_deblock_range(); gen_sao_range(); gen_alf_range(); gen_residual_range(); gen_arith_range(); gen_cabac_range()      # seeds of their own: the order does not matter
     print("done")

@@ -898,3 +898,150 @@ def SAO_EMU(m):
 
 def ALF_EMU(m):
     return (m[0] <= 136 and m[3] in (0, 2)) or m[0] == 512       # +-127 coefficients on the alternating and the noise picture: one CTU, and partial CTUs right and below; every (fixed set, class) pair
+
+
+# ---- residual coding and the arithmetic coder at their range edges (tests/golden/residual_range.npz, arith_range.npz, cabac_range.npz) ----
+# a meta row of residual_range.npz: the block, what steers its syntax, which row of the fixture's table of start states it begins from, and the pattern its levels follow
+RC_META = ("comp", "w", "h", "dq", "ts", "mts", "mi", "isp", "start", "pat", "p0", "p1", "p2", "seed")
+RC_SINGLE, RC_ONES, RC_MAX, RC_NOISE, RC_REM_CTX, RC_REM_BYP, RC_GROUPS, RC_CHAIN, RC_TS_THR = range(9)
+RC_COUNTERS = 58
+RC_BUDGET_MID_GROUP, RC_REM, RC_POS0, RC_INFERRED_SIG, RC_GROUP_FLAG, RC_LAST_FULL_X, RC_LAST_FULL_Y, RC_ZERO_OUT_SKIP, RC_MAX_MODELS_IN_64 = 0, 1, 37, 49, 50, 54, 55, 56, 57
+# remainder forms that 16-bit levels cannot reach (bins = the coded remainder, escape with the longest prefix needs (bins >> rice) - 5 >= 4095): behind context-coded bins
+# bins = (|level| - 4) >> 1 <= 16382, so Rice parameters 2 and 3 stop short of it; in the bypass pass bins <= 32768, so Rice parameter 3 does (32768 >> 3 = 4096); residual_codingTS
+# has Rice parameters 0..2 and bins = (|level| - 10) >> 1 <= 16379
+RC_REM_UNREACHABLE = ((0, 2, 2), (0, 3, 2), (1, 3, 2), (2, 2, 2), (2, 3, 0), (2, 3, 1), (2, 3, 2))
+
+
+def _rc_coded_area(w, h, mi):
+    """the part of a w x h block that carries levels: 32 x 32 of a 64-sample side, 16 of a 32-point side with an explicit MTS pair"""
+    lim = lambda n: n if mi == 1 else (16 if (mi > 1 and n == 32) else min(n, 32))
+    return lim(w), lim(h)
+
+
+def residual_range_levels(m, chain_lev=None):
+    """the int16 levels (h x w) of a meta row of residual_range.npz; chain_lev: the fixture's stored block for the RC_CHAIN row, which a search made and no seed regenerates"""
+    r = dict(zip(RC_META, (int(v) for v in m)))
+    w, h, pat, p0, p1, p2 = r["w"], r["h"], r["pat"], r["p0"], r["p1"], r["p2"]
+    zw, zh = _rc_coded_area(w, h, r["mi"])
+    g = np.random.default_rng(r["seed"])
+    lev = np.zeros((h, w), np.int64)
+    yy, xx = np.mgrid[0:zh, 0:zw]
+    if pat == RC_SINGLE:
+        lev[p1, p0] = p2
+    elif pat == RC_ONES:                         # all +-1: dense, or on a checkerboard
+        v = np.where(g.random((zh, zw)) < 0.5, -1, 1)
+        lev[:zh, :zw] = v if p0 == 0 else v * ((xx + yy) & 1 == 0)
+    elif pat == RC_MAX:                          # the ends of the level range
+        lev[:zh, :zw] = (32767, -32768)[p0] if p0 < 2 else np.where((xx + yy) & 1, -32768, 32767)
+    elif pat == RC_NOISE:                        # heavy-tailed noise at a density
+        v = np.rint(g.standard_cauchy((zh, zw)) * (1.5, 4.0, 40.0)[p0]).clip(-32768, 32767)
+        lev[:zh, :zw] = v * (g.random((zh, zw)) < (0.1, 0.4, 0.9)[p0])
+        if not lev.any():
+            lev[0, 0] = 1
+    elif pat == RC_REM_CTX:                      # the level under test at (0, 0), its template sum set by the neighbour to the right (or below, in a block one sample wide)
+        lev[0, 0] = -p0 if p2 else p0
+        if p1:
+            lev[(1, 0) if zw == 1 else (0, 1)] = p1
+    elif pat == RC_REM_BYP:                      # the same in the bypass pass: the groups coded before the first one use the budget up (levels of 2: four bins each); p2 & 3 of them are odd
+        lev[:zh, :zw] = 2
+        lev[:4, :4] = 0
+        for k in range(p2 & 3):
+            lev[zh - 1 - (k == 1), zw - 1 - (k == 2)] = 3
+        lev[0, 0] = -p0 if p2 & 4 else p0
+        if p1:
+            lev[0, 1] = p1
+    elif pat == RC_GROUPS:                       # p0: which 4 x 4 groups carry levels (bit = group's raster index); p1 0: only at the group's first scan position (top left), 1: all over it
+        gw = zw // 4
+        for k in range(gw * (zh // 4)):
+            if (p0 >> k) & 1:
+                y0, x0 = 4 * (k // gw), 4 * (k % gw)
+                if p1:
+                    lev[y0:y0 + 4, x0:x0 + 4] = g.integers(-3, 4, (4, 4))
+                lev[y0, x0] = 1 + (k & 1)
+    elif pat == RC_CHAIN:                        # as many context models inside 64 scan positions as the generator's search found a legal block to use
+        lev[:] = chain_lev
+    elif pat == RC_TS_THR:                       # transform skip: the level under test at (1, 1), the Rice parameter set by its left neighbour
+        lev[1, 1] = -p0 if p2 else p0
+        if p1:
+            lev[1, 0] = p1
+    assert lev.any() and np.abs(lev[:zh, :zw]).max() <= 32768 and lev.min() >= -32768 and lev.max() <= 32767, r
+    return lev.astype(np.int16)
+
+
+def sparse_states(s0, s1, e0, e1):
+    """the models that moved: (index, s0', s1') rows"""
+    idx = np.flatnonzero((s0 != e0) | (s1 != e1))
+    return np.stack([idx, e0[idx], e1[idx]], axis=1).astype(np.uint16).reshape(-1, 3)
+
+
+def residual_range_expected():
+    """every case of residual_range.npz: (meta row as a dict, levels, start states, expected: bits of the levels alone, their end states, rc_last, the writer's bits, end states, bytes)"""
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "residual_range.npz"))
+    g = {k: z[k] for k in z.files}                       # (an .npz member is decompressed at every access)
+    so, wo, bo = g["moved_off"], g["wmoved_off"], g["byte_off"]
+    out = []
+    for i, m in enumerate(g["meta"]):
+        r = dict(zip(RC_META, (int(v) for v in m)))
+        s0, s1 = g["starts"][r["start"]]
+        ends = []
+        for rows in (g["moved"][so[i]:so[i + 1]], g["wmoved"][wo[i]:wo[i + 1]]):
+            e0, e1 = s0.copy(), s1.copy()
+            e0[rows[:, 0]] = rows[:, 1]; e1[rows[:, 0]] = rows[:, 2]
+            ends.append((e0, e1))
+        out.append(dict(r, i=i, lev=residual_range_levels(m, g["chain_lev"]), s0=s0, s1=s1, bits=int(g["bits"][i]), end=ends[0], last=int(g["last"][i]), wbits=int(g["wbits"][i]), wend=ends[1],
+                        bytes=g["bytes"][bo[i]:bo[i + 1]]))
+    return out
+
+
+def check_residual_range(fn, form, cases):
+    """fn(levels of n blocks, w, h, comp, tools, ts_allowed, mts_allowed, mts_idx, s0, s1, form) -> (bits, s0', s1', rc_last, byte strings) on the given cases of
+    residual_range.npz, blocks that share their parameters in one call; returns the number of blocks checked"""
+    groups = {}
+    for c in cases:
+        groups.setdefault((c["comp"], c["w"], c["h"], c["dq"], c["ts"], c["mts"], c["mi"], c["start"]), []).append(c)
+    n = 0
+    for (comp, w, h, dq, ts, mts, mi, start), cs in groups.items():
+        bits, e0, e1, last, by = fn(np.concatenate([c["lev"].ravel() for c in cs]), w, h, comp, 0x40 if dq else 0, ts, mts, mi, cs[0]["s0"], cs[0]["s1"], form)
+        for k, c in enumerate(cs):
+            key = {q: c[q] for q in RC_META}
+            if form == 3:
+                assert np.array_equal(by[k], c["bytes"]), ("bytes", form, key)
+                assert int(bits[k]) == c["wbits"] and np.array_equal(e0[k], c["wend"][0]) and np.array_equal(e1[k], c["wend"][1]), ("writer's bits / states", key)
+            else:
+                assert int(bits[k]) == c["bits"], ("bits", form, key, int(bits[k]), c["bits"])
+                assert np.array_equal(e0[k], c["end"][0]) and np.array_equal(e1[k], c["end"][1]), ("end states", form, key)
+            assert int(last[k]) == c["last"], ("rc_last", form, key)
+            n += 1
+    return n
+
+
+def residual_counter_conditions(cnt, chain_max):
+    """every branch counter of orc_residual_counters over the fixture's cases: non-zero, but for the remainder forms no 16-bit level reaches; the greatest number of models
+    in a run of 64 positions is the one recorded when the fixture was made"""
+    cnt = np.asarray(cnt)
+    rem = cnt[RC_REM:RC_REM + 36].reshape(3, 4, 3)
+    for p in range(3):
+        for r in range(4):
+            for f in range(3):
+                assert (rem[p, r, f] == 0) == ((p, r, f) in RC_REM_UNREACHABLE), ("remainder code: pass, Rice parameter, form", p, r, f, int(rem[p, r, f]))
+    rest = np.concatenate([cnt[:RC_REM], cnt[RC_POS0:RC_MAX_MODELS_IN_64]])
+    assert (rest > 0).all(), ("counter", np.flatnonzero(rest == 0))
+    assert int(cnt[RC_MAX_MODELS_IN_64]) == chain_max and chain_max > 64, (int(cnt[RC_MAX_MODELS_IN_64]), chain_max)      # more than rc_chain groups in one round
+
+
+def arith_counter_conditions(cnt):
+    """each of the four ways buffered bytes resolve (writeOut without / with a carry, finish with / without one) occurred, with a run of at least 3 buffered bytes"""
+    cnt = np.asarray(cnt).reshape(4, 2)
+    assert (cnt[:, 0] > 0).all() and (cnt[:, 1] >= 3).all(), cnt.tolist()
+
+
+def cabac_range_bins(kind):
+    """the bin strings of cabac_range.npz: 2000 zeros | 2000 ones | alternating | 1999 zeros and a one | 1999 ones and a zero"""
+    b = np.zeros(2000, np.uint8)
+    if kind == 1 or kind == 4:
+        b[:] = 1
+    if kind == 2:
+        b[1::2] = 1
+    if kind >= 3:
+        b[-1] ^= 1
+    return b

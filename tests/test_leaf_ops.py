@@ -46,6 +46,18 @@ def _cabac(lib, limit):
         rows = rd[rd[:, 0] == lam]
         cost = pkg.rd_cost_batch(lam, rows[:, 1].astype(np.uint64), rows[:, 2].astype(np.uint64), lib_path=lib)
         assert np.array_equal(cost, rows[:, 3])                 # identical doubles: two roundings, no FMA (CL/RdCost.cpp:63-74)
+    # the ends of the ranges (cabac_range.npz): every QP the C-ABI takes and beyond, every adaptation rate into saturation and out of it, operands up to 2^62
+    import oracle_lib as O
+    r = np.load(os.path.join(G, "cabac_range.npz"))
+    for i, qp in list(enumerate(r["qps"]))[::(7 if limit else 1)]:
+        s0, s1 = pkg.ctx_init(int(qp), lib_path=lib)
+        assert np.array_equal(s0, r["s0"][i]) and np.array_equal(s1, r["s1"][i]), qp
+    for (ctx, rt, a0, b0, kind, bits, e0, e1) in r["seq"][::(9 if limit else 1)]:
+        got = pkg.cabac_code_bins(int(a0), int(b0), int(ctx), O.cabac_range_bins(int(kind)), lib_path=lib)
+        assert got == (int(bits), int(e0), int(e1)), (ctx, rt, a0, b0, kind)
+    for lam in np.unique(r["lam"]):
+        k = r["lam"] == lam
+        assert np.array_equal(pkg.rd_cost_batch(lam, r["frac_bits"][k], r["dist"][k], lib_path=lib), r["cost"][k]), lam
 
 
 def _scan(lib, keys=None):
@@ -570,3 +582,105 @@ def test_mip_prediction():
     g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mip.npz"))
     cases = np.stack([g["meta"][:, 1], g["meta"][:, 2], g["meta"][:, 3], g["meta"][:, 0]], axis=1).astype(np.int32)
     assert np.array_equal(vv.mip_pred_batch(cases, g["refs"]), g["preds"])
+
+
+# ---- residual coding in its four forms and the arithmetic coder (tests/golden/residual_range.npz, arith_range.npz) ----
+_RC_CASES = []
+
+
+def _rc_cases():
+    """the cases of residual_range.npz, regenerated once"""
+    import oracle_lib as O
+    if not _RC_CASES:
+        _RC_CASES.extend(O.residual_range_expected())
+    return _RC_CASES
+
+
+def _rc_form_takes(c, form):
+    """what a form exists for: the wave forms have no transform-skip syntax, form 1 stages at most 256 levels in the wave's LDS slot (the blocks the search keeps there)"""
+    return not (form in (1, 2) and c["mi"] == 1) and not (form == 1 and c["w"] * c["h"] > 256)
+
+
+def _residual_range(lib, form, comp, pick=lambda c: True):
+    import oracle_lib as O
+    vv = importlib.import_module(PKGNAME + ".vvcx")
+    cases = [c for c in _rc_cases() if c["comp"] == comp and _rc_form_takes(c, form) and pick(c)]
+    return O.check_residual_range(lambda *a: vv.residual_coding_batch(*a, lib_path=lib), form, cases)
+
+
+def _arith_range(lib, step=1):
+    vv = importlib.import_module(PKGNAME + ".vvcx")
+    g = np.load(os.path.join(G, "arith_range.npz"))
+    o_off = b_off = n = 0
+    for i, (qp, nops, nbytes) in enumerate(g["meta"]):
+        ops = g["ops"][o_off:o_off + 3 * nops]; o_off += 3 * int(nops)
+        exp = g["bytes"][b_off:b_off + nbytes]; b_off += int(nbytes)
+        if i % step == 0:
+            assert np.array_equal(vv.arith_encode(int(qp), ops, lib_path=lib), exp), (i, qp, ops[:12])
+            n += 1
+    return n
+
+
+def _rc_emu_pick():
+    """the cases the CPU emulation runs: for every branch counter of the oracle one case that raises it, every kind of pattern on its smallest block, the block with more
+    than 64 models in a run, and a thin spread over the rest; blocks of at most 256 levels, but for the skipped groups of a zeroed area, which need 16 x 32"""
+    import ctypes as C
+    import oracle_lib as O
+    from test_oracle_golden import _orc_residual_leaf
+    L = O.lib()
+    cnt = np.zeros(O.RC_COUNTERS, np.int64)
+    small = [c for c in _rc_cases() if c["w"] * c["h"] <= 256 or (c["w"], c["h"], c["pat"]) == (16, 32, O.RC_NOISE)]
+    need = set(range(O.RC_COUNTERS)) - {O.RC_MAX_MODELS_IN_64} - set(O.RC_REM + (p * 4 + r) * 3 + f for (p, r, f) in O.RC_REM_UNREACHABLE)
+    ids = set()
+    for c in small:
+        L.orc_residual_counters(cnt.ctypes.data_as(C.c_void_p))
+        _orc_residual_leaf(L, c, 0)
+        L.orc_residual_counters(cnt.ctypes.data_as(C.c_void_p))
+        hit = set(np.flatnonzero(cnt).tolist()) & need
+        if hit or c["pat"] == O.RC_CHAIN:
+            ids.add(c["i"]); need -= hit
+    assert not need, sorted(need)
+    ids |= set(c["i"] for c in small[::40])
+    return ids
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("comp", [0, 1])
+@pytest.mark.parametrize("form", [0, 1, 2, 3])
+def test_gpu_residual_coding_forms_match_reference_at_range_edges(form, comp):
+    """vvcx_residual_coding_batch on every vector of residual_range.npz: the single-lane estimator, the wave estimator from LDS and from device memory (rc_chain with more
+    than 64 models in a round among them) return the stored bits, end states of all models and last position; the writer returns the bytes the REFERENCE's reader parsed"""
+    n = _residual_range(None, form, comp)
+    assert n == len([c for c in _rc_cases() if c["comp"] == comp and _rc_form_takes(c, form)]) and n > 1000
+
+
+@pytest.mark.gpu
+def test_gpu_transform_skip_bits_of_the_leaf_and_of_the_batch_agree():
+    """the bits vvcx_transform_skip_batch reports for the levels it chose are the bits form 0 of vvcx_residual_coding_batch spends on the same levels from the same states"""
+    from test_oracle_golden import _range_cases
+    vv = importlib.import_module(PKGNAME + ".vvcx")
+    n = 0
+    for c in _range_cases("d")[::4]:
+        s0, s1 = c["ctx"]
+        l, o, aa, kk, bits = vv.transform_skip_batch(c["resi"], c["w"], c["h"], c["bd"], c["qp"] + 6 * (c["bd"] - 8), c["lam"], s0, s1)
+        if aa[0] > 0:
+            b0 = vv.residual_coding_batch(l, c["w"], c["h"], 0, 0x40, 1, 1, 1, s0, s1, 0)[0]
+            assert int(b0[0]) == int(bits[0]), (c["bd"], c["qp"], c["w"], c["h"], c["pat"])
+            n += 1
+    assert n > 30
+
+
+@pytest.mark.gpu
+def test_gpu_arithmetic_coder_matches_reference_at_range_edges():
+    """vvcx_arith_encode (arith_bin, arith_bins_ep, arith_trm, arith_write_out, arith_finish) on every constructed string of arith_range.npz: the REFERENCE's bytes"""
+    assert _arith_range(None) == 728
+
+
+def test_emulated_residual_coding_forms_and_arithmetic_coder_match_reference(emu_so):
+    """a slice of residual_range.npz with at least one case per branch counter, and every seventh string of arith_range.npz, through the CPU emulation of the kernel sources"""
+    ids = _rc_emu_pick()
+    pick = lambda c: c["i"] in ids
+    for comp in (0, 1):
+        ns = [_residual_range(emu_so, form, comp, pick) for form in range(4)]
+        assert ns[0] == ns[3] >= ns[2] >= ns[1] > 20, ns
+    assert _arith_range(emu_so, 7) == 104

@@ -1064,3 +1064,84 @@ def test_deblock_quilt_covers_every_pair_of_transform_sizes():
             assert ((t[:, 1] >> 7) == ((t[:, 1] + t[:, 3] - 1) >> 7)).all() and ((t[:, 2] >> 7) == ((t[:, 2] + t[:, 4] - 1) >> 7)).all()      # no CU straddles a CTU
         assert (rows[rows[:, 0] == 1][:, 5] == 0).all() and ((rows[:, 5] > 0).sum() > 40)
 
+
+
+# ---- residual coding, the arithmetic coder and the bin model at their range edges (residual_range.npz, arith_range.npz, cabac_range.npz) ----
+def _orc_residual_leaf(L, c, write):
+    """the oracle on one case of residual_range.npz -> (bits, end s0, end s1, last, bytes)"""
+    L.orc_residual_leaf.argtypes = [C.c_void_p] * 3 + [C.c_int] * 8 + [C.c_void_p] * 5 + [C.c_int]
+    bits = C.c_uint64(); e0 = np.zeros(386, np.uint16); e1 = np.zeros(386, np.uint16); last = C.c_int(); out = np.zeros(6 * c["w"] * c["h"] + 64, np.uint8)
+    lev = np.ascontiguousarray(c["lev"])
+    n = L.orc_residual_leaf(P(c["s0"]), P(c["s1"]), P(lev), c["w"], c["h"], c["comp"], c["dq"], c["ts"], c["mts"], c["mi"], int(write), C.byref(bits), P(e0), P(e1), C.byref(last), P(out), len(out))
+    assert n >= 0
+    return bits.value, e0, e1, last.value, out[:n]
+
+
+def test_residual_coding_at_range_edges():
+    """orc_residual_coding_tu on every case of residual_range.npz: the bytes are the ones from which the REFERENCE's CABACReader parsed the levels back, consumed exactly and
+    ending in the same states of all 386 models, when the fixture was made; the bits and end states of the levels alone are the same walk without the transform indices.  The
+    branch counters show that the cases reach what they were built for: the budget running out inside a group, every reachable form of the remainder code per Rice parameter in
+    both passes and in residual_codingTS, the three outcomes at the zero position for every quantiser state, inferred significances, both group flags under both contexts,
+    last-position prefixes without a terminating zero, skipped groups of a zeroed area, and more than 64 context models inside one run of 64 scan positions."""
+    L = O.lib()
+    g = np.load(os.path.join(G, "residual_range.npz"))
+    cases = O.residual_range_expected()
+    assert len(cases) == len(g["meta"]) > 6000
+    cnt = np.zeros(O.RC_COUNTERS, np.int64); tot = np.zeros(O.RC_COUNTERS, np.int64)
+    for c in cases:
+        key = {q: c[q] for q in O.RC_META}
+        L.orc_residual_counters(P(cnt))
+        bits, e0, e1, last, _ = _orc_residual_leaf(L, c, 0)
+        L.orc_residual_counters(P(cnt))
+        tot[:O.RC_MAX_MODELS_IN_64] += cnt[:O.RC_MAX_MODELS_IN_64]; tot[O.RC_MAX_MODELS_IN_64] = max(tot[O.RC_MAX_MODELS_IN_64], cnt[O.RC_MAX_MODELS_IN_64])
+        assert (bits, last) == (c["bits"], c["last"]) and np.array_equal(e0, c["end"][0]) and np.array_equal(e1, c["end"][1]), ("levels alone", key)
+        bits, e0, e1, last, by = _orc_residual_leaf(L, c, 1)
+        assert np.array_equal(by, c["bytes"]), ("bytes", key)
+        assert (bits, last) == (c["wbits"], c["last"]) and np.array_equal(e0, c["wend"][0]) and np.array_equal(e1, c["wend"][1]), ("writer", key)
+    O.residual_counter_conditions(tot, int(g["chain_max"][0]))
+    # the cases the issue of this fixture names are all there
+    shapes = lambda f: set((c["w"], c["h"]) for c in cases if f(c))
+    assert len(shapes(lambda c: c["comp"] == 0 and not c["isp"] and c["mi"] == 0)) == 25 and len(shapes(lambda c: c["comp"] == 1)) == 19
+    assert shapes(lambda c: c["isp"]) >= set(s for n in (8, 16, 32, 64) for s in ((1, n), (2, n), (n, 1), (n, 2)) if s[0] * s[1] >= 16)
+    assert len(shapes(lambda c: c["mi"] == 1)) == 16 and shapes(lambda c: c["mi"] > 1) == {(32, 32), (32, 8), (16, 32), (32, 16)}
+    assert set(c["start"] for c in cases) == set(range(6)) and set(c["dq"] for c in cases) == {0, 1}
+    assert any(c["lev"].min() == -32768 for c in cases) and any(c["lev"].max() == 32767 for c in cases)
+
+
+def test_arithmetic_coder_at_range_edges():
+    """orc_arith_encode on the constructed operation strings of arith_range.npz (bytes of the REFERENCE's BinEncoder_Std): runs of 3, 8 and 40 buffered bytes that resolve in
+    writeOut and in finish, each with and without a carry (the counters), bypass runs of every length, terminating bins around a range of 256, saturated models"""
+    L = O.lib()
+    g = np.load(os.path.join(G, "arith_range.npz"))
+    cnt = np.zeros(8, np.int64); tot = np.zeros((4, 2), np.int64)
+    o_off = b_off = 0
+    lengths = set()
+    for (qp, n, nbytes) in g["meta"]:
+        ops = np.ascontiguousarray(g["ops"][o_off:o_off + 3 * n]); o_off += 3 * int(n)
+        exp = g["bytes"][b_off:b_off + nbytes]; b_off += int(nbytes)
+        out = np.zeros(int(nbytes) + 16, np.uint8)
+        L.orc_arith_counters(P(cnt))
+        assert L.orc_arith_encode(int(qp), P(ops), int(n), P(out), len(out)) == nbytes and np.array_equal(out[:nbytes], exp), (qp, ops[:12])
+        L.orc_arith_counters(P(cnt)); c2 = cnt.reshape(4, 2); tot[:, 0] += c2[:, 0]; tot[:, 1] = np.maximum(tot[:, 1], c2[:, 1])
+        lengths |= set(int(r[2]) for r in ops.reshape(-1, 3) if r[0] == 1)
+    O.arith_counter_conditions(tot)
+    assert lengths == set(range(1, 33)) and len(g["meta"]) > 700
+
+
+def test_cabac_model_and_rdcost_at_range_edges():
+    """cabac_range.npz: the I-slice initialisation at every QP from -12 to 70 (the reference clips to 0..63), one model of every adaptation rate driven into saturation and
+    flipped from the extreme initial states, calcRdCost with operands up to 2^62 at the lambdas of slice QP -12 .. 63"""
+    L = O.lib()
+    g = np.load(os.path.join(G, "cabac_range.npz"))
+    assert g["qps"].tolist() == list(range(-12, 71))
+    for i, qp in enumerate(g["qps"]):
+        s0 = np.zeros(386, np.uint16); s1 = np.zeros(386, np.uint16)
+        L.orc_ctx_init(int(qp), P(s0), P(s1))
+        assert np.array_equal(s0, g["s0"][i]) and np.array_equal(s1, g["s1"][i]), qp
+    assert len(set(g["seq"][:, 1].tolist())) == 11
+    for (ctx, rt, a0, b0, kind, bits, e0, e1) in g["seq"]:
+        a = np.array([a0], np.uint16); b = np.array([b0], np.uint16); bins = O.cabac_range_bins(int(kind))
+        assert (L.orc_ctx_code_bins(P(a), P(b), int(ctx), P(bins), len(bins)), int(a[0]), int(b[0])) == (bits, e0, e1), (ctx, rt, a0, b0, kind)
+    for lam, fb, d, cost in zip(g["lam"], g["frac_bits"], g["dist"], g["cost"]):
+        assert L.orc_calc_rd_cost(C.c_double(lam), int(fb), int(d)) == cost, (lam, fb, d)
+    assert int(g["frac_bits"].max()) == 1 << 62 and (1 << 53) + 1 in g["dist"].tolist()
