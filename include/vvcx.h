@@ -368,6 +368,11 @@ int  vvcx_depquant_batch(const int16_t *org, const int16_t *pred, int w, int h, 
  * mode for DM / CCLM chroma), from which the kernel set and the transposition follow after the wide-angle mapping of the block shape */
 int  vvcx_lfnst_depquant_batch(const int16_t *org, const int16_t *pred, int w, int h, int bit_depth, int qp, int comp, int lfnst_idx, int intra_dir, int cbf_cb, double lambda,
                                const uint16_t *s0, const uint16_t *s1, int n, int16_t *lev, int16_t *rec, uint64_t *sse, uint8_t *cbf, int device);
+/* the trellis alone on n luma coefficient blocks (w x h each, 4..32 per side, int16 as the forward transforms leave them) quantised side by side by one wavefront
+ * against one set of context models, as the full-RD rounds of the search quantise the candidates of a node: lev = the levels, abs_sum[i] = DepQuant::quant's absSum of
+ * block i.  *max_items (may be NULL) receives the most blocks one wavefront takes for the shape (at most 16); n beyond it is VVCX_ERR_ARG */
+int  vvcx_depquant_items(const int16_t *coef, int w, int h, int bit_depth, int qp, double lambda, const uint16_t *s0, const uint16_t *s1, int n,
+                         int16_t *lev, int32_t *abs_sum, int *max_items, int device);
 /* transform skip of n luma residual blocks (4..32 per side; VVCX_TOOL_TS): ≙ the {DCT2, TS} pruning of TrQuant::transformNxN (CL/TrQuant.cpp:1049-1124; keep = the
  * transform-skip candidate survives), xTransformSkip 1394-1440, QuantRDOQ::xRateDistOptQuantTS (CL/QuantRDOQ.cpp:1243-1483, reached through DepQuant::quant for
  * MTS_SKIP blocks) with rates from the context models s0 / s1 and the quantiser's lambda, Quant::dequant + xITransformSkip 996-1041 (resi_out), and the fractional

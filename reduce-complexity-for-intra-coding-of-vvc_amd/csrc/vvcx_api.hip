@@ -51,6 +51,7 @@ extern "C" __global__ void vvcx_deblock_kernel_u8(VxDeblockParams p);
 extern "C" __global__ void vvcx_deblock_kernel_u16(VxDeblockParams p);
 extern "C" __global__ void vvcx_jccr_sign_kernel_u8(VxFrameDev *frames, int wc, int hc);
 extern "C" __global__ void vvcx_jccr_sign_kernel_u16(VxFrameDev *frames, int wc, int hc);
+extern "C" __global__ void vvcx_leaf_dq_items_kernel(VxParams p, const uint16_t *ctx, int16_t *coef, uint8_t *nodes, int n, int w, int h, int *out);
 extern "C" __global__ void vvcx_leaf_dq_kernel(VxParams p, const uint16_t *ctx, const int16_t *org, int16_t *rec, int16_t *lev, int32_t *tmp, int w, int h, int qp, int comp, int mts, int cbf_cb, unsigned long long *out, int lf, int lfdir);
 extern "C" __global__ void vvcx_leaf_ts_kernel(VxParams p, const uint16_t *ctx, const int16_t *resi, int16_t *lev, int16_t *resi_out, int32_t *tmp, int w, int h, int qp, int *out, unsigned long long *bits);
 extern "C" __global__ void vvcx_lmcs_map_kernel_u8(const uint8_t *src, uint8_t *dst, int w, int h, int stride, const int16_t *lut);
@@ -1902,6 +1903,34 @@ static int depquant_batch_impl(const int16_t *org, const int16_t *pred, int w, i
   HIPCHK(hipMemcpy(lev, dlev.p, bytes, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(rec, drec.p, bytes, hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(o.data(), dout.p, (size_t) n * 16, hipMemcpyDeviceToHost));
   for (int i = 0; i < n; i++) { sse[i] = o[(size_t) i * 2]; cbf[i] = (uint8_t) o[(size_t) i * 2 + 1]; }
+  return VVCX_OK;
+}
+
+extern "C" int vvcx_depquant_items(const int16_t *coef, int w, int h, int bit_depth, int qp, double lambda, const uint16_t *s0, const uint16_t *s1, int n,
+                                   int16_t *lev, int32_t *abs_sum, int *max_items, int device)
+{
+  if (!coef || !lev || !abs_sum || !s0 || !s1 || n < 0 || n > 16 || !pow2_block(w, h) || w < 4 || h < 4 || w > 32 || h > 32 || (bit_depth != 8 && bit_depth != 10) || qp < 0 || qp > 75 ||
+      !(lambda > 0.0)) return fail(VVCX_ERR_ARG, "bad argument");
+  ON_DEVICE(device);
+  const size_t P = (size_t) w * h;
+  DevBuf<int16_t> dcoef; DevBuf<uint8_t> dnodes; DevBuf<int> dout; DevBuf<uint16_t> dctx; DevBuf<VxDqConst> dtab;
+  HIPCHK(dcoef.alloc(P * 16)); HIPCHK(dnodes.alloc(4 * P * 16)); HIPCHK(dout.alloc(17)); HIPCHK(dctx.alloc(2 * VXD_NUM_CTX)); HIPCHK(dtab.alloc(48));
+  HIPCHK(hipMemset(dcoef.p, 0, P * 16 * 2)); HIPCHK(hipMemset(dnodes.p, 0, 4 * P * 16)); HIPCHK(hipMemset(dout.p, 0, 17 * sizeof(int)));
+  if (n) HIPCHK(hipMemcpy(dcoef.p, coef, P * n * 2, hipMemcpyHostToDevice));
+  { uint16_t kept[2 * VXD_NUM_CTX]; ctx_from_reference_order(s0, s1, kept); HIPCHK(hipMemcpy(dctx.p, kept, sizeof kept, hipMemcpyHostToDevice)); }
+  VxDqConst tab[48]; memset(tab, 0, sizeof tab);
+  for (int lsum = 2; lsum <= 12; lsum++) tab[lsum] = dq_consts_of(lsum, bit_depth, qp, lambda);
+  HIPCHK(hipMemcpy(dtab.p, tab, sizeof tab, hipMemcpyHostToDevice));
+  VxParams p; memset(&p, 0, sizeof p);
+  p.bit_depth = bit_depth; p.tools = VVCX_TOOL_DEPQUANT; p.dq_consts = dtab.p;
+  hipLaunchKernelGGL(vvcx_leaf_dq_items_kernel, dim3(1), dim3(VXD_NT), 0, 0, p, dctx.p, dcoef.p, dnodes.p, n, w, h, dout.p);
+  HIPCHK(hipGetLastError());
+  int o[17];
+  HIPCHK(hipMemcpy(o, dout.p, sizeof o, hipMemcpyDeviceToHost));
+  if (max_items) *max_items = o[16];
+  if (n > o[16]) return fail(VVCX_ERR_ARG, "more blocks than one wave takes for the shape");
+  if (n) HIPCHK(hipMemcpy(lev, dcoef.p, P * n * 2, hipMemcpyDeviceToHost));
+  for (int i = 0; i < n; i++) abs_sum[i] = o[i];
   return VVCX_OK;
 }
 

@@ -21,6 +21,17 @@
 #ifndef VXD_SERIAL_PRIO
 #define VXD_SERIAL_PRIO 0      // s_setprio level of the serial phases (trellis position loop, mode controller).  Measured: 0 / 2 / 3 give 179.1 / 178.7 / 178.3 CTU/s (profiles/r04_ab_runs.txt): no gain, left off
 #endif
+// Work the result does not need, taken out of the chain one part at a time; each part has its own switch so that it can be measured alone (DESIGN.md sections 6 and 8.1,
+// profiles/trellis_chain_ab.txt, profiles/trellis_chain_stamps_*.txt).  The first two halve their phases and are on; the third did not shorten the position loop and is off.
+#ifndef VXD_DQ_EOS_CLOSED
+#define VXD_DQ_EOS_CLOSED 1    // 4x4 coefficient groups: the template sums a path takes into the next group from 17 packed neighbour terms instead of 16 x 5 decoded slots.  Group ends 1.40 -> 0.58 * 10^11 wave clocks per frame
+#endif
+#ifndef VXD_DQ_LAST_SCAN
+#define VXD_DQ_LAST_SCAN 1     // last-position offsets: one lane per entry and a segmented prefix sum, once per call where the items share their models.  Tables / offsets 1.16 -> 0.57 * 10^11
+#endif
+#ifndef VXD_DQ_TROW_EARLY
+#define VXD_DQ_TROW_EARLY 0    // the template sum of the next position read by the source state at the top of the position and gathered with the other parent members: the state update
+#endif                         // outside the group ends stayed at 4.5 * 10^11 and the candidate costs took the read's wait (2.99 -> 3.29 * 10^11, measured in a build that also ran two positions per loop trip); alone 156.4 CTU/s against the parent's 155.4 / 156.9: off
 
 // 16 bytes / 16 half-words kept as scalar members (arrays indexed with a run-time value would be placed in scratch memory by the compiler)
 struct U4 { unsigned a, b, c, d; };
@@ -135,6 +146,14 @@ __device__ inline long long dq_dd(const VxDqConst &q, long long scaledOrg, int q
 }
 __device__ inline int dq_sig_off(int ch, int diag) { return ch ? (diag < 2 ? 4 : 0) : (diag < 2 ? 8 : diag < 5 ? 4 : 0); }            // xSetScanInfo 402-419
 __device__ inline int dq_gtx_off(int ch, int diag) { return ch ? (diag < 1 ? 6 : 1) : (diag < 1 ? 16 : diag < 3 ? 11 : diag < 10 ? 6 : 1); }
+// What one neighbour level (byte b_ of the node word w_) adds to a template sum, in the layout of a template row entry: sumNum [0,3), sumAbs1 [3,8), sumAbs from bit 8.
+// A template has at most five neighbours, so the two low fields cannot carry (5, 25); sumAbs is clamped to 127 after the terms are added (dq_tpl_clamp).
+__device__ inline unsigned dq_tpl_term(unsigned w, int b)
+{
+  const unsigned a = (w >> (8 * b)) & 255u, a1 = 4u + (a & 1u);
+  return (unsigned) (a != 0) | ((a < a1 ? a : a1) << 3) | (a << 8);
+}
+__device__ inline unsigned dq_tpl_clamp(unsigned s) { return s > 0x7FFFu ? (s & 0xFFu) | 0x7F00u : s; }
 
 // n_items blocks (1..16) of w x h.  Item i (quad i of the wave): coefficients cf_base + i * cf_stride (int16 — the forward transforms keep 15 bits
 // + sign — raster order, stride w; LDS or HBM), replaced by its levels; rate terms from context set ci0 + i * ci_step with the cbf context
@@ -253,8 +272,28 @@ __device__ __noinline__ void wave_depquant_batch(int n_items, int16_t *cf_base, 
   };
   auto riceBits = [&](int rpar, unsigned v) -> int { return TAB ? (int) riceTab[rpar * 32 + (int) v] << 15 : dq_rice_bits(rpar, v); };
   auto sbbBits = [&](int sbbc, int bin) -> int { return TAB ? sbbTab[sbbc * 2 + bin] : dq_fb(ci, R.sbbBase + sbbc, bin); };
-  // ---- last-position offsets per group index (RateEstimator::xSetLastCoeffOffset 488-568): lane k of the quad takes the entries k, k + 4, ...
-  if (valid) {
+  // ---- last-position offsets per group index (RateEstimator::xSetLastCoeffOffset 488-568)
+  // Items that price against one model set share the offsets: lane 16 * xy + id takes entry id of x / y - one read of each bin of its model, then the sum over the entries
+  // before it as a prefix sum over the 16 lanes.  The x entries are kept once (item 0's area), the y entries per item with the item's cbf difference added, as before.
+  const bool lastShared = VXD_DQ_LAST_SCAN && (ci_step == 0 || n_items == 1);
+  const int *lastX = lastShared ? (const int *) wk : lastb;
+  if (lastShared) {
+    const int xy = (lane >> 4) & 1, id = lane & 15;
+    const int size = xy ? h : w, l2 = ilog2i(size);
+    const int base = (xy ? VX_CTX_LastY : VX_CTX_LastX)[ch];
+    const int sh = comp == 0 ? (l2 + 1) >> 2 : imin(2, size >> 3), lo = comp == 0 ? L.t.last_prefix[l2] : 0;
+    const int maxId = L.t.group_idx[imin(32, size) - 1];
+    const bool inner = id < maxId;                          // the entries that code a further prefix bin
+    const unsigned f1 = inner ? (unsigned) dq_fb(ci0, base + lo + (id >> sh), 1) : 0u, f0 = inner ? (unsigned) dq_fb(ci0, base + lo + (id >> sh), 0) : 0u;
+    unsigned s = f1;
+#pragma unroll
+    for (int d = 1; d < 16; d <<= 1) { const unsigned o = (unsigned) __shfl((int) s, id >= d ? lane - d : lane); if (id >= d) s += o; }
+    const unsigned b = s - f1 + (id > 3 ? (unsigned) ((id - 2) >> 1) << 15 : 0u) + f0;
+    if (lane < 16 && id <= maxId) ((int *) wk)[id] = (int) b;
+    const int cbfDelta = (valid && cbf_ctx >= 0) ? dq_fb(ci, cbf_ctx, 1) - dq_fb(ci, cbf_ctx, 0) : 0;
+#pragma unroll
+    for (int e = 0; e < 12; e += 4) { const unsigned by = (unsigned) __shfl((int) b, 16 + imin(e + k, 15)); if (valid && e + k < 10) lastb[10 + e + k] = (int) (by + (unsigned) cbfDelta); }
+  } else if (valid) {
     const int cbfDelta = cbf_ctx >= 0 ? dq_fb(ci, cbf_ctx, 1) - dq_fb(ci, cbf_ctx, 0) : 0;
     for (int e = k; e < 20; e += 4) {
       const int xy = e >= 10, id = xy ? e - 10 : e;
@@ -348,6 +387,10 @@ __device__ __noinline__ void wave_depquant_batch(int n_items, int16_t *cf_base, 
     const int absC = iabs(cnext);
     if (valid && sp > 0 && sp - 1 <= first) cnext = (int) (int16_t) trel[sp - 1];
     { const DqS t = prv; prv = cur; cur = t; }
+#if VXD_DQ_TROW_EARLY
+    // this lane as SOURCE state: the entry of its template row for the position coded next, read here, off the chain decision -> parent -> template
+    const int tsrc = (int) tmrows[((prv.pk >> 27) & 7) * 16 + nin];
+#endif
     // ---- decision of target state k (xDecide 1455-1517)
     long long dc = 0x7fffffffffffffffll >> 2; int dsrc = 0, dnz = 0, dlev = -1;          // dsrc: 0 none, 1 start, 2 from the "A/zero" source state, 3 from the "B" source state, 4 sub-block skipped
     if (zeroed) {
@@ -401,7 +444,7 @@ __device__ __noinline__ void wave_depquant_batch(int n_items, int16_t *cf_base, 
       }
       if (!(k & 1)) {                                       // checkRdCostStart 1032-1050 into decisions 0 (candidate 0) and 2 (candidate 2)
         const int stS = DQ_STEP(k), levS = DQ_LEV(stS);
-        const long long c = ddMine + (long long) (lastb[(gA >> 19) & 15] + lastb[10 + ((gA >> 23) & 15)]) + levBits(0, 0, levS);
+        const long long c = ddMine + (long long) (lastX[(gA >> 19) & 15] + lastb[10 + ((gA >> 23) & 15)]) + levBits(0, 0, levS);
         if (c < dc) { dc = c; dsrc = 1; dnz = 1; dlev = levS; }
       }
 #undef DQ_STEP
@@ -421,9 +464,15 @@ __device__ __noinline__ void wave_depquant_batch(int n_items, int16_t *cf_base, 
       // parent state (a previous state of the quad) — every lane shuffles, the lanes whose decision has no such parent discard the result
       // (the "A/zero" source of target k is lane [0,2,1,3][k] of the quad, the "B" source lane [1,3,0,2][k]: two quad permutations and a select)
       struct { int pk, rem; unsigned long long anc; U4 lev; } P;
+#if VXD_DQ_TROW_EARLY
+      int tpar;
+#endif
       {
         const bool fromA = dsrc == 2;
 #define DQ_PARENT(x_) dq_parent((int) (x_), fromA)
+#if VXD_DQ_TROW_EARLY
+        tpar = DQ_PARENT(tsrc);
+#endif
         P.pk = DQ_PARENT(prv.pk); P.rem = DQ_PARENT(prv.rem);
         P.anc = (unsigned long long) (unsigned) DQ_PARENT((unsigned) prv.anc) | ((unsigned long long) (unsigned) DQ_PARENT((unsigned) (prv.anc >> 32)) << 32);
         P.lev.a = (unsigned) DQ_PARENT(prv.lev.a); P.lev.b = (unsigned) DQ_PARENT(prv.lev.b); P.lev.c = (unsigned) DQ_PARENT(prv.lev.c); P.lev.d = (unsigned) DQ_PARENT(prv.lev.d);
@@ -452,7 +501,11 @@ __device__ __noinline__ void wave_depquant_batch(int n_items, int16_t *cf_base, 
           const int trow = fromPrev ? ((P.pk >> 27) & 7) : 4;
           VX_CHECK(trow <= 4 && nin < 16);
           pk = (pk & ~(7 << 27)) | (trow << 27);
+#if VXD_DQ_TROW_EARLY
+          const int t = fromPrev ? tpar : 0;
+#else
           const int t = (int) tmrows[trow * 16 + nin];
+#endif
           int sumAbs = t >> 8, sumAbs1 = (t >> 3) & 31, sumNum = t & 7;
           {
             // (the neighbours' places are the same for every lane: register-indexed reads instead of select trees)
@@ -485,15 +538,58 @@ __device__ __noinline__ void wave_depquant_batch(int n_items, int16_t *cf_base, 
         // the path as it leaves this group: field 0 = this state and the group's significance, the older groups one field up
         const unsigned long long anc = (pAnc << 4) | (unsigned long long) (unsigned) (k + 1) | ((numSig != 0) ? 8ull : 0ull);
         VX_CHECK(g >= 1 && (g * 4 + k) * 16 + 16 <= node_room);
-        if (alive) { VX_GLOBAL uint32_t *hl = (VX_GLOBAL uint32_t *) (nd + (size_t) (g * 4 + k) * 16); hl[0] = lv.a; hl[1] = lv.b; hl[2] = lv.c; hl[3] = lv.d; }
-        wave_sync();
         // the groups right of, below and diagonally below the next group: their distance in group-scan order picks the ancestor field
-        const unsigned ng = geo.grp[g - 1]; const int nsx = (int) (ng & 15), nsy = (int) (ng >> 4);
-        const int gR = nsx < wsbb - 1 ? grp_inv[nsy * wsbb + nsx + 1] : -1, gB = nsy < hsbb - 1 ? grp_inv[(nsy + 1) * wsbb + nsx] : -1;
-        const int gD = (gR >= 0 && gB >= 0) ? grp_inv[(nsy + 1) * wsbb + nsx + 1] : -1;
+        const unsigned ng = (unsigned) uni((int) geo.grp[g - 1]); const int nsx = (int) (ng & 15), nsy = (int) (ng >> 4);
+        const int gR = nsx < wsbb - 1 ? uni((int) grp_inv[nsy * wsbb + nsx + 1]) : -1, gB = nsy < hsbb - 1 ? uni((int) grp_inv[(nsy + 1) * wsbb + nsx]) : -1;
+        const int gD = (gR >= 0 && gB >= 0) ? uni((int) grp_inv[(nsy + 1) * wsbb + nsx + 1]) : -1;
         const unsigned fR = gR >= 0 ? (unsigned) (anc >> (4 * (gR - g))) & 15u : 0u, fB = gB >= 0 ? (unsigned) (anc >> (4 * (gB - g))) & 15u : 0u;
         const unsigned fD = gD >= 0 ? (unsigned) (anc >> (4 * (gD - g))) & 15u : 0u;
         const int sigN = ((fR & 8u) || (fB & 8u)) ? 1 : 0;
+#if VXD_DQ_EOS_CLOSED
+        if (lcw == 2 && lch == 2) {
+          // 4x4 groups: a template reaches columns 0-1 of the right group, rows 0-1 of the group below and sample (0, 0) of the diagonal one; where those 17 levels sit in
+          // the nodes is fixed by the diagonal scan of a group (raster -> scan index: 0 2 5 9 / 1 4 8 12 / 3 7 11 14 / 6 10 13 15).  A neighbour group that is the group
+          // just left (the first two groups of a block: field 0 of anc is this state) is the path's own level word, still in registers; every other node was written at an
+          // earlier group end, so its load does not wait for this one's store.
+          unsigned r0 = 0, r1 = 0, r2 = 0, b0 = 0, b1 = 0, b2 = 0, b3 = 0, d0 = 0;
+          if (alive) {
+            VX_CHECK(!(fR & 7u) || (gR >= g && gR - g < 16 && (gR * 4 + (int) (fR & 7u) - 1) * 16 + 16 <= node_room));
+            VX_CHECK(!(fB & 7u) || (gB >= g && gB - g < 16 && (gB * 4 + (int) (fB & 7u) - 1) * 16 + 16 <= node_room));
+            VX_CHECK(!(fD & 7u) || (gD > g && gD - g < 16 && (gD * 4 + (int) (fD & 7u) - 1) * 16 + 16 <= node_room));
+            VX_CHECK(gR != g || (fR & 7u) == (unsigned) (k + 1)); VX_CHECK(gB != g || (fB & 7u) == (unsigned) (k + 1));
+            if (gR == g) { r0 = lv.a; r1 = lv.b; r2 = lv.c; }
+            else if (fR & 7u) { const VX_GLOBAL uint32_t *p_ = (const VX_GLOBAL uint32_t *) (nd + (size_t) (gR * 4 + (int) (fR & 7u) - 1) * 16); r0 = p_[0]; r1 = p_[1]; r2 = p_[2]; }
+            if (gB == g) { b0 = lv.a; b1 = lv.b; b2 = lv.c; b3 = lv.d; }
+            else if (fB & 7u) { const VX_GLOBAL uint32_t *p_ = (const VX_GLOBAL uint32_t *) (nd + (size_t) (gB * 4 + (int) (fB & 7u) - 1) * 16); b0 = p_[0]; b1 = p_[1]; b2 = p_[2]; b3 = p_[3]; }
+            if (fD & 7u) { const VX_GLOBAL uint32_t *p_ = (const VX_GLOBAL uint32_t *) (nd + (size_t) (gD * 4 + (int) (fD & 7u) - 1) * 16); d0 = p_[0]; }
+            VX_GLOBAL uint32_t *hl = (VX_GLOBAL uint32_t *) (nd + (size_t) (g * 4 + k) * 16); hl[0] = lv.a; hl[1] = lv.b; hl[2] = lv.c; hl[3] = lv.d;
+          }
+          wave_sync();
+          if (alive) {
+            // row k: this state's entry into the next group.  Entry = scan index of sample (x, y) of the group, whose neighbours outside the group are those of
+            // {(x+1,y) (x+2,y) (x+1,y+1) (x,y+1) (x,y+2)} with x + dx > 3 or y + dy > 3; the entries 0, 1, 2, 4 (x, y < 2) have none and stay the zeros the rows start as.
+            // (the right group's part first, each entry stored as soon as it is complete: few values are live at a time next to the three roles of the loop)
+            uint16_t *row = tmrows + k * 16;
+            unsigned p11, p13, p14, p15;
+            {
+              const unsigned R00 = dq_tpl_term(r0, 0), R01 = dq_tpl_term(r0, 1), R02 = dq_tpl_term(r0, 3), R03 = dq_tpl_term(r1, 2);      // column 0 of the right group, rows 0..3
+              const unsigned R10 = dq_tpl_term(r0, 2), R11 = dq_tpl_term(r1, 0), R12 = dq_tpl_term(r1, 3), R13 = dq_tpl_term(r2, 2);      // column 1
+              row[5] = (uint16_t) dq_tpl_clamp(R00); row[8] = (uint16_t) dq_tpl_clamp(R01); row[9] = (uint16_t) dq_tpl_clamp(R00 + R10 + R01); row[12] = (uint16_t) dq_tpl_clamp(R01 + R11 + R02);
+              p11 = R02; p13 = R03; p14 = R02 + R12 + R03; p15 = R03 + R13;
+            }
+            {
+              const unsigned B00 = dq_tpl_term(b0, 0), B01 = dq_tpl_term(b0, 2), B02 = dq_tpl_term(b1, 1), B03 = dq_tpl_term(b2, 1);      // row 0 of the group below, columns 0..3
+              const unsigned B10 = dq_tpl_term(b0, 1), B11 = dq_tpl_term(b1, 0), B12 = dq_tpl_term(b2, 0), B13 = dq_tpl_term(b3, 0);      // row 1
+              row[3] = (uint16_t) dq_tpl_clamp(B00); row[6] = (uint16_t) dq_tpl_clamp(B00 + B10 + B01); row[7] = (uint16_t) dq_tpl_clamp(B01); row[10] = (uint16_t) dq_tpl_clamp(B01 + B11 + B02);
+              row[11] = (uint16_t) dq_tpl_clamp(p11 + B02); row[13] = (uint16_t) dq_tpl_clamp(p13 + B02 + B12 + B03); row[14] = (uint16_t) dq_tpl_clamp(p14 + B03);
+              row[15] = (uint16_t) dq_tpl_clamp(p15 + dq_tpl_term(d0, 0) + B03 + B13);
+            }
+          }
+        } else
+#endif
+        {
+        if (alive) { VX_GLOBAL uint32_t *hl = (VX_GLOBAL uint32_t *) (nd + (size_t) (g * 4 + k) * 16); hl[0] = lv.a; hl[1] = lv.b; hl[2] = lv.c; hl[3] = lv.d; }
+        wave_sync();
         // the three nodes (16 level bytes each) whose levels the next group's templates look at
         // (a group beyond the block's edge - the coded 32 x 32 region's for bigger blocks - is an all-zero node: it adds nothing to the sums)
         typedef unsigned dq_v16u __attribute__((vector_size(64)));
@@ -518,6 +614,7 @@ __device__ __noinline__ void wave_depquant_batch(int n_items, int16_t *cf_base, 
             }
           }
           if (alive) tmrows[k * 16 + id] = (uint16_t) (sumNum + (sumAbs1 << 3) + (imin(127, sumAbs) << 8));      // row k: this state's entry into the next group
+        }
         }
         if (alive) {
           pk = dq_put(pk, 0, 5, 0); pk = dq_put(pk, 8, 2, 0); pk = dq_put(pk, 5, 3, k + 1); pk = dq_put(pk, 16, 2, sigN + 1);

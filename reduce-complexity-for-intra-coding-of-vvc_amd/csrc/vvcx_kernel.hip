@@ -4671,6 +4671,24 @@ extern "C" __global__ void __launch_bounds__(NT, VXD_WPE) vvcx_leaf_dq_kernel(Vx
   else wave_code_block<false>(org + b, 0, 0, rec + b, lev + b, tmp + (size_t) blockIdx.x * 2048, w, h, bd, qp, lane, sse, cbf, -1, nullptr, comp, CI_CUR, cbf_cb, lf, lf ? lfnst_mode(lfdir, w, h) : 0);
   if (lane == 0) { out[blockIdx.x * 2] = sse; out[blockIdx.x * 2 + 1] = (unsigned long long) cbf; }
 }
+// the batched trellis as the full-RD rounds run it (dq_trellis_phase): the node's rate tables by the whole workgroup, then n luma coefficient blocks of one shape side by
+// side in one wave_depquant_batch<2> call of wave 0, all against the given models.  coef: n blocks of w x h (replaced by their levels), nodes: 4 * positions bytes per block;
+// out[i] = absSum of block i, out[16] = the most blocks one wave takes for the shape (n beyond it: nothing is run)
+extern "C" __global__ void __launch_bounds__(NT, VXD_WPE) vvcx_leaf_dq_items_kernel(VxParams p, const uint16_t *ctx, int16_t *coef, uint8_t *nodes, int n, int w, int h, int *out)
+{
+  if (VTX == 0) { L.par = p; L.lmcs_tab = 0; }
+  load_tables();
+  for (int i = VTX; i < NCTX; i += NT) { L.ctxs[CI_CUR].s0[i] = ctx[i]; L.ctxs[CI_CUR].s1[i] = ctx[NCTX + i]; }
+  __syncthreads();
+  dq_build_tables(0);
+  const int wave = uni(VTX >> 6), lane = VTX & 63, total = imin(32, w) * imin(32, h);
+  const int ipw = imin(16, (int) sizeof(WaveMem) / (240 + 2 * total));
+  if (wave != 0) return;
+  if (lane == 0) out[16] = ipw;
+  if (n < 1 || n > ipw) return;
+  wave_depquant_batch<2>(n, coef, w * h, nodes, 4 * total, 0, 0, CI_CUR, 0, VX_CTX_QtCbf[0], 0u, w, h, 0, 0, 0, lane);
+  if (lane < n) out[lane] = L.dq_abs[lane];
+}
 // transform skip of one residual block per workgroup (tests/golden/ts.npz): the pruning decision against the DCT-II sum, xTransformSkip, RDOQ-TS from the given context
 // models, Quant::dequant + xITransformSkip, and the bits residual_codingTS spends on the levels.  resi_out must be zero on entry; out = {absSum, keep} per block
 extern "C" __global__ void __launch_bounds__(NT, VXD_WPE) vvcx_leaf_ts_kernel(VxParams p, const uint16_t *ctx, const int16_t *resi, int16_t *lev, int16_t *resi_out, int32_t *tmp,

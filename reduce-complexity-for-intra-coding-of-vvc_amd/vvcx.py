@@ -622,6 +622,20 @@ def depquant_batch(org, pred, w, h, bit_depth, qp, comp, mts_idx, cbf_cb, lam, s
     return lev.reshape(n, h, w), rec.reshape(n, h, w), sse, cbf
 
 
+def depquant_items(coef, w, h, bit_depth, qp, lam, s0, s1, device=0, lib_path=None):
+    """vvcx_depquant_items: n coefficient blocks [n, h, w] quantised side by side by one wavefront against one model set (the batched trellis of the full-RD rounds)
+    -> (levels int16 [n, h, w], absSum int32 [n], the most blocks one wavefront takes for the shape)"""
+    L = load_library(lib_path)
+    coef = np.ascontiguousarray(coef, np.int16).ravel()
+    s0 = np.ascontiguousarray(s0, np.uint16); s1 = np.ascontiguousarray(s1, np.uint16)
+    n = coef.size // (w * h)
+    lev = np.zeros(coef.size, np.int16); asum = np.zeros(max(n, 1), np.int32); cap = C.c_int(0)
+    L.vvcx_depquant_items.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    _chk(L, L.vvcx_depquant_items(coef.ctypes.data, w, h, bit_depth, qp, lam, s0.ctypes.data, s1.ctypes.data, n, lev.ctypes.data, asum.ctypes.data,
+                                  C.cast(C.pointer(cap), C.c_void_p), device))
+    return lev.reshape(n, h, w), asum[:n], cap.value
+
+
 def transform_skip_batch(resi, w, h, bit_depth, qp, lam, s0, s1, device=0, lib_path=None):
     """vvcx_transform_skip_batch: n residual blocks through the {DCT2, TS} pruning, xTransformSkip, RDOQ-TS, dequantisation + xITransformSkip and residual_codingTS's estimator"""
     L = load_library(lib_path)
