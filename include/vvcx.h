@@ -260,6 +260,7 @@ int   vvcx_alf_picture(int pic_w, int pic_h, int bit_depth, const vvcx_alf_aps *
 /* ---- the encoder side of ALF (EL/EncAdaptiveLoopFilter.cpp).  Call order of the loop-filter stage on bound pictures:
  *   vvcx_deblock_bound_frames -> vvcx_sao_statistics_bound_frames -> vvcx_sao_decide -> vvcx_sao_bound_frames
  *   -> vvcx_alf_statistics_bound_frames -> vvcx_alf_decide -> vvcx_alf_bound_frames
+ * and, for the bitstream, ... -> vvcx_alf_decide -> vvcx_rewrite_payload_bound_frames -> vvcx_get_payload (the rewrite reads no samples: before or after the filter calls).
  *
  * ≙ EncAdaptiveLoopFilter::deriveStatsForFiltering (EL/EncAdaptiveLoopFilter.cpp:2650-2745; getBlkStats 2746-2843, calcCovariance 2844-2965, m_alfWSSD off): the content of
  * AlfCovariance per CTU and class, gathered on the device from the original and the picture the ALF filter would read (after deblocking and SAO).  Per sample s and
@@ -303,8 +304,36 @@ int  vvcx_deblock_cu_table(int pic_w, int pic_h, int bit_depth, int qp, int qp_c
                            const int32_t *rows, int n_rows, uint16_t *y, uint16_t *cb, uint16_t *cr, int device);
 /* slice_data() payload of one completely coded tile of a bound frame: the bytes EncSlice::encodeSlice would hand to the NAL writer
  * for that brick (CABACWriter::coding_tree_unit per CTU, end_of_ctu / end_of_slice terminating bins, byte alignment;
- * EL/EncSlice.cpp:1884-2006).  Requires cfg.emit_payload.  buf is host memory */
+ * EL/EncSlice.cpp:1884-2006).  Requires cfg.emit_payload.  buf is host memory.  After the search the payload carries the coding trees only - no SAO / ALF CTU syntax, the
+ * bytes of a slice whose header switches both filters off - until vvcx_rewrite_payload_bound_frames has written it again with the pictures' parameters */
 int  vvcx_get_payload(vvcx_handle *h, int frame, int tile, uint8_t *buf, int cap, int *nbytes);
+/* ≙ the CTU-level loop-filter syntax CABACWriter::coding_tree_unit (EL/CABACWriter.cpp:254-309) writes in front of every coding tree: sao() / sao_block_pars /
+ * sao_offset_pars (323-462), codeAlfCtuEnableFlag (4700-4725), codeAlfCtuFilterIndex (4833-4892), codeAlfCtuAlternative (4920-4943).  The parameters exist only after the
+ * whole picture is searched, deblocked and analysed, but their bins lie inside each tile's arithmetic codeword: this call writes every tile's payload of the bound pictures
+ * a second time, from the CU tables and levels the search left on the device (what vvcx_get_cus / vvcx_get_levels return; no samples are read, so it may run before or
+ * after the loop-filter calls), one workgroup per (frame, tile), none waiting on another.  vvcx_get_payload / vvcx_get_substream_sizes then return the new bytes and sizes.
+ * Repeatable: a later call with other parameters, or with everything off (which gives the bytes of the search again), writes from the tables, never from earlier bytes.
+ * hdr[frame] (≙ the slice header): slice_sao_luma_flag, slice_sao_chroma_flag, tile_group_alf_enabled_flag Y / Cb / Cr.  sao = prm[frame][ctu][3] as vvcx_sao_decide
+ * returns them (may be NULL when no frame has SAO on); aps / slices / ctus as for vvcx_alf_bound_frames (slices, ctus NULL when no frame has ALF on; of a parameter set only
+ * num_chroma_alt is read).  trace_ops_per_tile > 0 also keeps up to that many coder operations per tile for vvcx_get_payload_ops.
+ * VVCX_ERR_STATE: no payload buffer (cfg.emit_payload), nothing bound, a CTU not coded yet.  VVCX_ERR_ARG, found on the host before anything is launched, for what the syntax
+ * cannot carry: SAO mode outside 0..2, type outside 0..4 (merge: 0..1), band outside 0..31, |offset| above (1 << (min(bit_depth, 10) - 5)) - 1, an edge-offset CTU with
+ * offset[0..1] < 0 or offset[2..3] > 0 (those signs are implicit), Cb and Cr of different mode or type (they share sao_type_idx_chroma and the edge class), a merge whose
+ * candidate CTU lies outside the tile or the picture or that is not set on all three components, a component that is not off in a slice that disables it; an ALF luma set
+ * outside 0..15 and 16..16 + n_luma_aps - 1, a chroma alternative >= num_chroma_alt of the slice's chroma set, a CTU flag of a component the slice disables.
+ * When sao is given, the records of EVERY frame are checked, also of a frame whose slice has SAO off: such a frame must carry all-off records (mode 0); likewise the CTU
+ * flags of a frame whose slice has ALF off must be 0 when ctus is given.  The work is enqueued on hip_stream, but the call BLOCKS until it has completed there (it
+ * synchronises the stream before it returns: the host tables it uploads must outlive the copies).  The slice header and the parameter-set NAL units are the caller's. */
+typedef struct vvcx_ctu_syntax { uint8_t sao_luma, sao_chroma, alf[3]; } vvcx_ctu_syntax;
+int   vvcx_rewrite_payload_bound_frames(vvcx_handle *h, const vvcx_ctu_syntax *hdr, const vvcx_sao_param *sao, const vvcx_alf_aps *aps, int n_aps,
+                                        const vvcx_alf_slice *slices, const vvcx_alf_ctu *ctus, int trace_ops_per_tile, void *hip_stream);
+float vvcx_last_rewrite_ms(const vvcx_handle *h);
+/* Diagnostic (it is what lets a test pin the rewritten bytes to the reference's BinEncoder_Std): the operation string the last rewrite coded for one tile, in the format of
+ * vvcx_arith_encode - ops[i] = {kind, a, b}, context models as the reference's flat indices (the models of the SAO / ALF syntax included, which vvcx_arith_encode does not
+ * keep).  With VVCX_TOOL_WPP the CTU rows of the tile follow one another; each ends with its terminating-bin operations ({2, 0, 0} behind every CTU but the last of the
+ * picture, then {2, 1, 0}), so the rows can be split.  ops may be NULL (max_ops 0) to query the count.  VVCX_ERR_STATE without a traced rewrite; VVCX_ERR_ARG when the
+ * tile coded more operations than the rewrite kept room for (*n_ops tells how many; the payload itself is complete all the same) or than max_ops. */
+int   vvcx_get_payload_ops(vvcx_handle *h, int frame, int tile, int32_t *ops, int max_ops, int *n_ops);
 /* ≙ the fork's GET_TRAINING_SET build (CL/TypeDef.h:54-56; EL/CABACWriter.cpp:515-855 writes the rows the forests of BIN/TEST.py are trained on): with a dump enabled every luma
  * node of the search that qualifies for the classifier (EL/EncCu.cpp:810-846, 933) leaves one row of 28 int32: the 26 features (EL/EncCu.cpp:863-1123), the complexity class
  * (0 simple, 1 fuzzy, 2 complex; 1127-1138) and the partition the full search chose at that node (0 none, 1 QT, 2 BT_H, 3 BT_V, 4 TT_H, 5 TT_V; -1: no encoding).  Rows

@@ -15,11 +15,14 @@
 #include "vvcx_dev.h"
 #include "vvcx_host.h"        // DevBuf, ON_DEVICE / DevGuard, HIPCHK
 #include "vvcx_tables.h"      // host copy of the constant tables (context init values)
+#include "vvcx_ctu_syntax_tables.h"      // the models of the SAO / ALF CTU syntax: flat indices, init values, rates
 
 extern "C" __global__ void vvcx_compress_kernel_u8(VxParams p);
 extern "C" __global__ void vvcx_compress_kernel_u16(VxParams p);
 extern "C" __global__ void vvcx_compress_wpp_kernel_u8(VxParams p);
 extern "C" __global__ void vvcx_compress_wpp_kernel_u16(VxParams p);
+extern "C" __global__ void vvcx_rewrite_kernel_u8(VxParams p, VxRewriteParams r);
+extern "C" __global__ void vvcx_rewrite_kernel_u16(VxParams p, VxRewriteParams r);
 extern "C" __global__ void vvcx_leaf_dist_kernel(const int16_t *a, const int16_t *b, int w, int h, int16_t *scr, unsigned long long *out);
 extern "C" __global__ void vvcx_leaf_pred_kernel_u8(VxParams p, const VxLeafPred *cases, int16_t *out, const int *out_off);
 extern "C" __global__ void vvcx_leaf_pred_kernel_u16(VxParams p, const VxLeafPred *cases, int16_t *out, const int *out_off);
@@ -107,6 +110,10 @@ struct vvcx_handle {
   DevBuf<long long> sao_stat_d; float last_sao_stats_ms;      // vvcx_sao_statistics_bound_frames
   DevBuf<VxAlfFrame> alf_tab_d; DevBuf<VxAlfCtu> alf_ctu_d; float last_alf_ms;      // vvcx_alf_bound_frames: per-frame tables and per-CTU choices (the picture copy is the SAO one)
   DevBuf<long long> alf_stat_luma_d, alf_stat_chroma_d; float last_alf_stats_ms;      // vvcx_alf_statistics_bound_frames
+  // vvcx_rewrite_payload_bound_frames: per-frame header flags, coded SAO parameters, ALF choices, the tile / sub-stream tables, start states, per-workgroup sync states,
+  // walk scratch and operation trace; the host copy of the last trace counts
+  DevBuf<VxCtuSynFrame> rw_hdr_d; DevBuf<VxSaoSyn> rw_sao_d; DevBuf<VxAlfCtu> rw_alf_d; DevBuf<uint8_t> rw_scratch_d; DevBuf<int32_t> rw_tab_d, rw_trace_d;
+  DevBuf<uint16_t> rw_ctx_d; DevBuf<uint32_t> rw_trace_n_d; std::vector<uint32_t> rw_trace_n; int rw_trace_cap; float last_rewrite_ms;
   // a submitted, not yet collected launch (vvcx_submit_ctus .. vvcx_wait_ctus): staging the async copies read from / write to stays alive here
   bool pending; hipStream_t pend_stream; int pend_n; VxCtuRes *pend_res; int pend_cap;
   std::vector<VxStreamDesc> pend_sd; std::vector<int32_t> pend_task_ctu; std::vector<int> pend_src, pend_next; VxDqConst pend_dq[17 * 96];
@@ -461,6 +468,7 @@ extern "C" int vvcx_bind_frames(vvcx_handle *h, const vvcx_frame *frames, int n)
   if (h->wpp_progress_d.p) HIPCHK(hipMemset(h->wpp_progress_d.p, 0, (size_t) n * h->nsub * 4));
   if (h->train_n_d.p) HIPCHK(hipMemset(h->train_n_d.p, 0, 4));
   h->next_idx.assign((size_t) n * h->nsub, 0);
+  h->rw_trace_n.clear(); h->rw_trace_cap = 0;
   return VVCX_OK;
 }
 
@@ -477,6 +485,30 @@ extern "C" int vvcx_resident_streams(const vvcx_handle *h)
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, VXD_NT, 0) != hipSuccess) return 0;
   { const char *e = getenv("VVCX_MAX_WG_PER_CU"); const int cap = e ? atoi(e) : 0; if (cap > 0 && cap < per_cu) per_cu = cap; }      // diagnostic: the rate against the workgroups sharing a CU
   return cus * per_cu;
+}
+
+// the launch parameters every kernel that codes CTU syntax reads (the search and the payload rewrite): picture and slice constants, the handle's device state
+static void stream_params(vvcx_handle *h, VxParams &p)
+{
+  memset(&p, 0, sizeof p);
+  p.pic_w = h->cfg.pic_w; p.pic_h = h->cfg.pic_h; p.bit_depth = h->cfg.bit_depth; p.chroma = h->cfg.chroma; p.tools = h->cfg.tools;
+  for (int k = 0; k < 2; k++) { p.min_qt[k] = h->cfg.min_qt[k]; p.max_bt_depth[k] = h->cfg.max_bt_depth[k]; p.max_bt_size[k] = h->cfg.max_bt_size[k]; p.max_tt_size[k] = h->cfg.max_tt_size[k]; p.qp_c[k] = h->sl.qp_c[k]; p.dist_weight[k] = h->sl.dist_weight[k]; }
+  p.ctus_w = h->ctus_w; p.ctus_h = h->ctus_h; p.uw = h->uw; p.uh = h->uh; p.qp = h->sl.qp;
+  p.lambda = h->sl.lambda;
+  { const int bdo = 6 * (h->cfg.bit_depth - 8); p.qp_tr = h->sl.qp + bdo; p.qp_tr_c[0] = h->sl.qp_c[0] + bdo; p.qp_tr_c[1] = h->sl.qp_c[1] + bdo;
+    // QpParam of the modes +-2: the mapping table's value (one table for all chroma) + pps_joint_cbcr_qp_offset (CbCrQpOffset -1, APP/EncAppCfg.cpp:1082)
+    int qj = h->sl.qp_c[0] - 1; qj = qj < -bdo ? -bdo : qj > 63 ? 63 : qj; p.qp_tr_j = qj + bdo; }
+  p.dist_scale = (double) (1 << 15) / h->sl.lambda;                       // CL/RdCost.cpp:79
+  p.sqrt_lambda_fp = sqrt(h->sl.lambda) * (1.0 / (double) (1 << 15));     // EL/IntraSearch.cpp:297
+  p.frames = h->frames_d.p; p.streams = h->streams_d.p; p.task_ctu = h->task_ctu_d.p; p.results = h->results_d.p; p.stream_ctx = h->stream_ctx_d.p;
+  p.payload = h->payload_d.p; p.payload_off = h->payload_off_d.p; p.payload_cap = h->payload_cap_d.p; p.arith_state = h->arith_d.p;
+  p.scratch = h->scratch_d.p; p.counters = h->counters_d.p; p.ntiles = h->ntiles; p.nsub = h->nsub; p.wpp_progress = h->wpp_progress_d.p; p.wpp_sync = h->wpp_sync_d.p;
+  p.train_rows = h->train_rows_d.p; p.train_n = h->train_n_d.p; p.train_cap = h->train_cap; p.wpp_sched = h->wpp_sched_d.p; p.wpp_rr = h->wpp_rr;
+  p.f_node = h->f_node_d.p; p.f_value = h->f_value_d.p; p.f_root = h->f_root_d.p; p.f_ntrees = h->f_ntrees; p.f_nclasses = h->f_nclasses;
+  for (int c = 0; c < 8; c++) p.f_classes[c] = h->f_classes[c];
+  p.lmcs_on = h->lmcs_on; p.lmcs_cadj_on = h->lmcs_on && h->sl.lmcs_chroma_adj; p.lmcs_min_bin = h->sl.lmcs_min_bin; p.lmcs_max_bin = h->sl.lmcs_max_bin;
+  for (int b = 0; b < 17; b++) p.lmcs_pivot[b] = h->lmcs_on ? h->lmcs_pivot[b] : 0;
+  for (int b = 0; b < 16; b++) p.lmcs_cadj[b] = h->lmcs_on ? h->lmcs_cadj[b] : 0;
 }
 
 // The enqueue half: everything up to and including the device-to-host copy of the CTU results goes onto `hip_stream`; nothing waits.
@@ -561,26 +593,8 @@ extern "C" int vvcx_submit_ctus(vvcx_handle *h, const vvcx_ctu_task *tasks, int 
   HIPCHK(hipMemcpyAsync(h->task_ctu_d.p, task_ctu.data(), sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, stream));
   HIPCHK(hipMemsetAsync(h->counters_d.p, 0, 56 * sizeof(unsigned long long), stream));
 
-  VxParams p; memset(&p, 0, sizeof p);
-  p.pic_w = h->cfg.pic_w; p.pic_h = h->cfg.pic_h; p.bit_depth = h->cfg.bit_depth; p.chroma = h->cfg.chroma; p.tools = h->cfg.tools;
-  for (int k = 0; k < 2; k++) { p.min_qt[k] = h->cfg.min_qt[k]; p.max_bt_depth[k] = h->cfg.max_bt_depth[k]; p.max_bt_size[k] = h->cfg.max_bt_size[k]; p.max_tt_size[k] = h->cfg.max_tt_size[k]; p.qp_c[k] = h->sl.qp_c[k]; p.dist_weight[k] = h->sl.dist_weight[k]; }
-  p.ctus_w = h->ctus_w; p.ctus_h = h->ctus_h; p.uw = h->uw; p.uh = h->uh; p.qp = h->sl.qp;
-  p.lambda = h->sl.lambda;
-  { const int bdo = 6 * (h->cfg.bit_depth - 8); p.qp_tr = h->sl.qp + bdo; p.qp_tr_c[0] = h->sl.qp_c[0] + bdo; p.qp_tr_c[1] = h->sl.qp_c[1] + bdo;
-    // QpParam of the modes +-2: the mapping table's value (one table for all chroma) + pps_joint_cbcr_qp_offset (CbCrQpOffset -1, APP/EncAppCfg.cpp:1082)
-    int qj = h->sl.qp_c[0] - 1; qj = qj < -bdo ? -bdo : qj > 63 ? 63 : qj; p.qp_tr_j = qj + bdo; }
-  p.dist_scale = (double) (1 << 15) / h->sl.lambda;                       // CL/RdCost.cpp:79
-  p.sqrt_lambda_fp = sqrt(h->sl.lambda) * (1.0 / (double) (1 << 15));     // EL/IntraSearch.cpp:297
-  p.frames = h->frames_d.p; p.streams = h->streams_d.p; p.task_ctu = h->task_ctu_d.p; p.results = h->results_d.p; p.stream_ctx = h->stream_ctx_d.p;
-  p.payload = h->payload_d.p; p.payload_off = h->payload_off_d.p; p.payload_cap = h->payload_cap_d.p; p.arith_state = h->arith_d.p;
-  p.scratch = h->scratch_d.p; p.scratch_per_stream = per_stream; p.counters = h->counters_d.p; p.ntiles = h->ntiles; p.nsub = h->nsub; p.wpp_progress = h->wpp_progress_d.p; p.wpp_sync = h->wpp_sync_d.p;
-  p.train_rows = h->train_rows_d.p; p.train_n = h->train_n_d.p; p.train_cap = h->train_cap; p.wpp_sched = h->wpp_sched_d.p; p.wpp_rr = h->wpp_rr;
-  p.f_node = h->f_node_d.p; p.f_value = h->f_value_d.p; p.f_root = h->f_root_d.p; p.f_ntrees = h->f_ntrees; p.f_nclasses = h->f_nclasses;
-  for (int c = 0; c < 8; c++) p.f_classes[c] = h->f_classes[c];
-  p.n_streams = ns;
-  p.lmcs_on = h->lmcs_on; p.lmcs_cadj_on = h->lmcs_on && h->sl.lmcs_chroma_adj; p.lmcs_min_bin = h->sl.lmcs_min_bin; p.lmcs_max_bin = h->sl.lmcs_max_bin;
-  for (int b = 0; b < 17; b++) p.lmcs_pivot[b] = h->lmcs_on ? h->lmcs_pivot[b] : 0;
-  for (int b = 0; b < 16; b++) p.lmcs_cadj[b] = h->lmcs_on ? h->lmcs_cadj[b] : 0;
+  VxParams p; stream_params(h, p);
+  p.scratch_per_stream = per_stream; p.n_streams = ns;
   if (h->cfg.tools & VVCX_TOOL_DEPQUANT) {
     // the quantiser's lambda of a component: TrQuant::setLambdas / selectLambda (EL/EncSlice.cpp:107-149, EL/IntraSearch.cpp:2889) = lambda / distortion weight for chroma
     VxDqConst *tab = h->pend_dq; memset(tab, 0, sizeof h->pend_dq);
@@ -971,7 +985,7 @@ public:
   }
   static int max_q(int bd) { return (1 << (std::min(bd, 10) - 5)) - 1; }      // SampleAdaptiveOffset::getMaxOffsetQVal
 private:
-  static const int kFirst = 287;                        // Ctx::SaoMergeFlag in the reference's flat order (ContextSetCfg); SaoTypeIdx follows
+  static const int kFirst = VX_CTX_REF_SaoMergeFlag;    // Ctx::SaoMergeFlag in the reference's flat order (ContextSetCfg); SaoTypeIdx follows
   uint16_t s0_[2], s1_[2];
   void bypass(int n) { bits += (uint64_t) n << 15; }
   void coded(int which, bool bin)
@@ -2094,6 +2108,162 @@ extern "C" int vvcx_arith_encode(int qp, const int32_t *ops, int nops, uint8_t *
   if (nb > (uint32_t) cap) return fail(VVCX_ERR_ARG, "buffer too small: %u bytes needed", nb);
   HIPCHK(hipMemcpy(out, dby.p, nb, hipMemcpyDeviceToHost));
   *nbytes = (int) nb;
+  return VVCX_OK;
+}
+
+// ≙ what CABACWriter::coding_tree_unit writes in front of every coding tree (EL/CABACWriter.cpp:254-309: sao 323-462, codeAlfCtuEnableFlag 4700-4725, codeAlfCtuFilterIndex
+// 4833-4892, codeAlfCtuAlternative 4920-4943).  The parameters exist only after the picture has been searched and analysed, so every tile's payload is written once more,
+// from the CU maps and level planes that persist on the device (vvcx_kernel.hip rewrite_tile).  Everything the syntax cannot carry is refused here, before any launch.
+static int rewrite_check(const vvcx_handle *h, const vvcx_ctu_syntax *hdr, const vvcx_sao_param *sao, const vvcx_alf_aps *aps, int n_aps, const vvcx_alf_slice *slices,
+                         const vvcx_alf_ctu *ctus, std::vector<VxCtuSynFrame> &hd, std::vector<VxAlfCtu> &alf)
+{
+  const int cw = h->ctus_w, nctu = cw * h->ctus_h, bd = h->cfg.bit_depth, maxQ = (1 << ((bd < 10 ? bd : 10) - 5)) - 1;      // SampleAdaptiveOffset::getMaxOffsetQVal
+  hd.assign((size_t) h->n_frames, VxCtuSynFrame());
+  if (ctus) alf.assign((size_t) h->n_frames * nctu, VxAlfCtu());
+  if (n_aps < 0 || n_aps > 8 || (n_aps > 0 && !aps)) return fail(VVCX_ERR_ARG, "ALF: %d parameter sets (0..8)", n_aps);
+  for (int f = 0; f < h->n_frames; f++) {
+    VxCtuSynFrame &o = hd[(size_t) f];
+    memset(&o, 0, sizeof o);
+    o.sao_luma = hdr[f].sao_luma != 0; o.sao_chroma = hdr[f].sao_chroma != 0;
+    for (int c = 0; c < 3; c++) o.alf[c] = hdr[f].alf[c] != 0;
+    if (!h->cfg.chroma && (o.sao_chroma || o.alf[1] || o.alf[2])) return fail(VVCX_ERR_ARG, "frame %d: chroma syntax enabled on a handle without chroma", f);
+    if ((o.sao_luma || o.sao_chroma) && !sao) return fail(VVCX_ERR_ARG, "frame %d has SAO on and no parameters were given", f);
+    if ((o.alf[0] || o.alf[1] || o.alf[2]) && (!slices || !ctus)) return fail(VVCX_ERR_ARG, "frame %d has ALF on and no slice / CTU choices were given", f);
+    if (sao) for (int a = 0; a < nctu; a++) {
+      const vvcx_sao_param *p = sao + ((size_t) f * nctu + a) * 3;
+      const int on[3] = { o.sao_luma, o.sao_chroma, o.sao_chroma };
+#define SAO_BAD(fmt, ...) return fail(VVCX_ERR_ARG, "SAO parameters of frame %d CTU %d: " fmt, f, a, ##__VA_ARGS__)
+      for (int c = 0; c < 3; c++) if (p[c].mode < 0 || p[c].mode > 2) SAO_BAD("component %d has mode %d", c, p[c].mode);
+      if (p[0].mode == 2 || p[1].mode == 2 || p[2].mode == 2) {
+        if (p[0].mode != 2 || p[1].mode != 2 || p[2].mode != 2 || p[1].type != p[0].type || p[2].type != p[0].type) SAO_BAD("a merge must be set on all three components alike");
+        if (p[0].type != 0 && p[0].type != 1) SAO_BAD("merge type %d", p[0].type);
+        if (!on[0] && !on[1]) SAO_BAD("a merge in a slice that has SAO off");
+        const int left = p[0].type == 0, src = left ? a - 1 : a - cw;
+        if ((left ? a % cw == 0 : a < cw) || h->ctu_tile[(size_t) src] != h->ctu_tile[(size_t) a]) SAO_BAD("no %s merge candidate in the tile", left ? "left" : "above");
+        continue;
+      }
+      for (int c = 0; c < 3; c++) {
+        if (p[c].mode == 0) continue;
+        if (!on[c]) SAO_BAD("component %d is on in a slice that has it disabled", c);
+        if (p[c].type < 0 || p[c].type > 4 || p[c].band < 0 || p[c].band > 31) SAO_BAD("component %d: type %d band %d", c, p[c].type, p[c].band);
+        for (int i = 0; i < 4; i++) {
+          const int v = p[c].offset[i];
+          if (v < -maxQ || v > maxQ) SAO_BAD("component %d: offset %d beyond +-%d", c, v, maxQ);
+          if (p[c].type != 4 && (i < 2 ? v < 0 : v > 0)) SAO_BAD("component %d: edge offset %d is %d, its sign is implicit", c, i, v);
+        }
+      }
+      if (p[1].mode != p[2].mode || (p[1].mode == 1 && p[1].type != p[2].type)) SAO_BAD("Cb and Cr share sao_type_idx_chroma and the edge class");
+#undef SAO_BAD
+    }
+    const bool alfOn = o.alf[0] || o.alf[1] || o.alf[2];
+    if (alfOn) {
+      const vvcx_alf_slice &sl = slices[f];
+      if (o.alf[0]) {
+        if (sl.n_luma_aps < 0 || sl.n_luma_aps > 8) return fail(VVCX_ERR_ARG, "ALF slice of frame %d: %d luma sets", f, sl.n_luma_aps);
+        for (int k = 0; k < sl.n_luma_aps; k++) if (sl.luma_aps[k] < 0 || sl.luma_aps[k] >= n_aps) return fail(VVCX_ERR_ARG, "ALF slice of frame %d: luma set %d of %d", f, sl.luma_aps[k], n_aps);
+        o.n_aps = (uint8_t) sl.n_luma_aps;
+      }
+      if (o.alf[1] || o.alf[2]) {
+        if (sl.chroma_aps < 0 || sl.chroma_aps >= n_aps || aps[sl.chroma_aps].num_chroma_alt < 1 || aps[sl.chroma_aps].num_chroma_alt > 8)
+          return fail(VVCX_ERR_ARG, "ALF slice of frame %d: chroma is on and chroma set %d of %d has no alternatives", f, sl.chroma_aps, n_aps);
+        o.n_alt = (uint8_t) aps[sl.chroma_aps].num_chroma_alt;
+      }
+    }
+    if (ctus) for (int a = 0; a < nctu; a++) {
+      const vvcx_alf_ctu &u = ctus[(size_t) f * nctu + a]; VxAlfCtu &d = alf[(size_t) f * nctu + a];
+      memset(&d, 0, sizeof d);
+      for (int c = 0; c < 3; c++) {
+        if (!u.flag[c]) continue;
+        if (!o.alf[c]) return fail(VVCX_ERR_ARG, "ALF: frame %d CTU %d has the flag of component %d set, which the slice disables", f, a, c);
+        d.flag[c] = 1;
+      }
+      if (u.flag[0]) { if (u.set < 0 || u.set >= 16 + o.n_aps) return fail(VVCX_ERR_ARG, "ALF: frame %d CTU %d uses luma filter set %d of %d", f, a, u.set, 16 + o.n_aps); d.set = u.set; }
+      for (int c = 1; c < 3; c++) if (u.flag[c]) { if (u.alt[c - 1] >= o.n_alt) return fail(VVCX_ERR_ARG, "ALF: frame %d CTU %d uses chroma alternative %d of %d", f, a, u.alt[c - 1], o.n_alt); d.alt[c - 1] = u.alt[c - 1]; }
+    }
+  }
+  return VVCX_OK;
+}
+static void ctx_state_islice(int id, int qp, uint16_t &s0, uint16_t &s1)      // one model of CtxStore::init (ctx_init_islice)
+{
+  qp = qp < 0 ? 0 : qp > 63 ? 63 : qp;
+  const int slope = (id >> 3) - 4, offset = ((id & 7) * 18) + 1;
+  int st = ((slope * (qp - 16)) >> 1) + offset;
+  st = st < 1 ? 1 : st > 127 ? 127 : st;
+  s0 = (uint16_t) ((st << 8) & 0x7FE0); s1 = (uint16_t) ((st << 8) & 0x7FFE);
+}
+static_assert(VXD_NUM_CS_CTX == VX_CS_NUM_CTX, "vvcx_dev.h and vvcx_ctu_syntax_tables.h disagree on the number of CTU-syntax models");
+static_assert(sizeof(VxSaoSyn) == sizeof(vvcx_sao_param) && sizeof(VxAlfCtu) == sizeof(vvcx_alf_ctu), "device copies of the C-ABI records");
+extern "C" int vvcx_rewrite_payload_bound_frames(vvcx_handle *h, const vvcx_ctu_syntax *hdr, const vvcx_sao_param *sao, const vvcx_alf_aps *aps, int n_aps,
+                                                 const vvcx_alf_slice *slices, const vvcx_alf_ctu *ctus, int trace_ops_per_tile, void *hip_stream)
+{
+  NOT_PENDING(h);
+  if (!h || !hdr || trace_ops_per_tile < 0) return fail(VVCX_ERR_ARG, "bad argument");
+  if (!h->payload_d.p) return fail(VVCX_ERR_STATE, "handle was created without emit_payload");
+  if (!h->n_frames || !h->have_slice) return fail(VVCX_ERR_STATE, "no bound frames / slice");
+  if (const int rc = require_all_coded(h, "the payload rewrite")) return rc;
+  std::vector<VxCtuSynFrame> hd; std::vector<VxAlfCtu> alf;
+  if (const int rc = rewrite_check(h, hdr, sao, aps, n_aps, slices, ctus, hd, alf)) return rc;
+  const int nctu = h->ctus_w * h->ctus_h, nwg = h->n_frames * h->ntiles;
+  // tile and sub-stream tables: tile_sub0[ntiles] | tile_nsub[ntiles] | sub_first[nsub + 1] | sub_ctu[nctu] | tile_of_ctu[nctu]
+  std::vector<int32_t> tab;
+  for (int t = 0; t < h->ntiles; t++) tab.push_back(h->tile_sub0[(size_t) t]);
+  for (int t = 0; t < h->ntiles; t++) tab.push_back(h->tile_nsub[(size_t) t]);
+  { int n = 0; for (int s = 0; s < h->nsub; s++) { tab.push_back(n); n += (int) h->sub_ctus[(size_t) s].size(); } tab.push_back(n); }
+  for (int s = 0; s < h->nsub; s++) for (int a : h->sub_ctus[(size_t) s]) tab.push_back(a);
+  for (int a = 0; a < nctu; a++) tab.push_back(h->ctu_tile[(size_t) a]);
+  uint16_t ctx0[VXD_RW_CTX];
+  ctx_init_islice(h->sl.qp, ctx0, ctx0 + VXD_NUM_CTX);
+  for (int k = 0; k < VX_CS_NUM_CTX; k++) ctx_state_islice(VX_CS_INIT_I[k], h->sl.qp, ctx0[2 * VXD_NUM_CTX + k], ctx0[2 * VXD_NUM_CTX + VX_CS_NUM_CTX + k]);
+  ON_DEVICE(h->cfg.device);
+  hipStream_t stream = (hipStream_t) hip_stream;
+  const bool saoOn = sao != nullptr, alfOn = ctus != nullptr;
+  HIPCHK(h->rw_hdr_d.reserve(hd.size())); HIPCHK(h->rw_tab_d.reserve(tab.size())); HIPCHK(h->rw_ctx_d.reserve((size_t) VXD_RW_CTX * (1 + (size_t) nwg)));
+  HIPCHK(h->rw_scratch_d.reserve((size_t) nwg * VXD_RW_SCRATCH)); HIPCHK(h->rw_trace_n_d.reserve((size_t) nwg));
+  if (saoOn) HIPCHK(h->rw_sao_d.reserve((size_t) h->n_frames * nctu * 3));
+  if (alfOn) HIPCHK(h->rw_alf_d.reserve(alf.size()));
+  if (trace_ops_per_tile) HIPCHK(h->rw_trace_d.reserve((size_t) nwg * 3 * (size_t) trace_ops_per_tile));
+  h->rw_trace_n.clear(); h->rw_trace_cap = 0;
+  HIPCHK(hipMemcpyAsync(h->rw_hdr_d.p, hd.data(), hd.size() * sizeof(VxCtuSynFrame), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(h->rw_tab_d.p, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(h->rw_ctx_d.p, ctx0, sizeof ctx0, hipMemcpyHostToDevice, stream));
+  if (saoOn) HIPCHK(hipMemcpyAsync(h->rw_sao_d.p, sao, (size_t) h->n_frames * nctu * 3 * sizeof(VxSaoSyn), hipMemcpyHostToDevice, stream));
+  if (alfOn) HIPCHK(hipMemcpyAsync(h->rw_alf_d.p, alf.data(), alf.size() * sizeof(VxAlfCtu), hipMemcpyHostToDevice, stream));
+  VxParams p; stream_params(h, p);
+  VxRewriteParams r; memset(&r, 0, sizeof r);
+  r.hdr = h->rw_hdr_d.p; r.sao = saoOn ? h->rw_sao_d.p : nullptr; r.alf = alfOn ? h->rw_alf_d.p : nullptr;
+  r.tile_sub0 = h->rw_tab_d.p; r.tile_nsub = r.tile_sub0 + h->ntiles; r.sub_first = r.tile_nsub + h->ntiles; r.sub_ctu = r.sub_first + h->nsub + 1; r.tile_of_ctu = r.sub_ctu + nctu;
+  r.ctx0 = h->rw_ctx_d.p; r.sync = h->rw_ctx_d.p + VXD_RW_CTX; r.scratch = h->rw_scratch_d.p;
+  r.trace = trace_ops_per_tile ? h->rw_trace_d.p : nullptr; r.trace_n = h->rw_trace_n_d.p; r.trace_cap = trace_ops_per_tile;
+  // one workgroup per (frame, tile), VXD_NT threads each: thread 0 codes the tile, the others exist only to stage the constant tables (load_tables strides by VXD_NT) and leave
+  HIPCHK(hipEventRecord(h->ev0, stream));
+  if (h->cfg.bit_depth == 8) hipLaunchKernelGGL(vvcx_rewrite_kernel_u8, dim3((unsigned) nwg), dim3(VXD_NT), 0, stream, p, r);
+  else hipLaunchKernelGGL(vvcx_rewrite_kernel_u16, dim3((unsigned) nwg), dim3(VXD_NT), 0, stream, p, r);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(h->ev1, stream));
+  HIPCHK(hipStreamSynchronize(stream));             // (the host tables above must outlive the copies)
+  HIPCHK(hipEventElapsedTime(&h->last_rewrite_ms, h->ev0, h->ev1));
+  if (trace_ops_per_tile) {
+    h->rw_trace_n.resize((size_t) nwg);
+    HIPCHK(hipMemcpy(h->rw_trace_n.data(), h->rw_trace_n_d.p, (size_t) nwg * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    h->rw_trace_cap = trace_ops_per_tile;
+  }
+  return VVCX_OK;
+}
+extern "C" float vvcx_last_rewrite_ms(const vvcx_handle *h) { return h ? h->last_rewrite_ms : 0.f; }
+// diagnostic: the operation string the last rewrite coded for one tile (what pins its bytes to the reference's coder, tests/test_ctu_syntax.py)
+extern "C" int vvcx_get_payload_ops(vvcx_handle *h, int frame, int tile, int32_t *ops, int max_ops, int *n_ops)
+{
+  NOT_PENDING(h);
+  if (!h || !n_ops || max_ops < 0 || (!ops && max_ops) || frame < 0 || frame >= h->n_frames || tile < 0 || tile >= h->ntiles) return fail(VVCX_ERR_ARG, "bad argument");
+  if (!h->rw_trace_cap || h->rw_trace_n.size() != (size_t) h->n_frames * h->ntiles) return fail(VVCX_ERR_STATE, "no rewrite with a trace since the pictures were bound");
+  const size_t wg = (size_t) frame * h->ntiles + tile;
+  const uint32_t n = h->rw_trace_n[wg];
+  *n_ops = (int) n;
+  if (n > (uint32_t) h->rw_trace_cap) return fail(VVCX_ERR_ARG, "tile %d of frame %d coded %u operations, the rewrite kept room for %d per tile", tile, frame, n, h->rw_trace_cap);
+  if (!ops) return VVCX_OK;                            // count query
+  if (n > (uint32_t) max_ops) return fail(VVCX_ERR_ARG, "room for %d operations, the tile has %u", max_ops, n);
+  ON_DEVICE(h->cfg.device);
+  HIPCHK(hipMemcpy(ops, h->rw_trace_d.p + wg * 3 * (size_t) h->rw_trace_cap, (size_t) n * 3 * sizeof(int32_t), hipMemcpyDeviceToHost));
   return VVCX_OK;
 }
 

@@ -145,6 +145,29 @@ struct VxAlfStatParams {
   int32_t clip[2][4];             // clipping value of bin b: luma, chroma
 };
 
+// payload rewrite (vvcx_rewrite_kernel_*, vvcx_kernel.hip): every tile's slice_data once more from the stored CU maps and levels, with the SAO / ALF CTU syntax
+// (CABACWriter::coding_tree_unit, EL/CABACWriter.cpp:254-309) in front of each coding tree.  One workgroup per (frame, tile), thread 0 codes; no workgroup waits on another
+#define VXD_NUM_CS_CTX  15                              // the models of that syntax (vvcx_ctu_syntax_tables.h VX_CS_NUM_CTX), kept beside the VXD_NUM_CTX ones
+#define VXD_RW_CTX      (2 * (VXD_NUM_CTX + VXD_NUM_CS_CTX))      // one set of states, uint16: s0[VXD_NUM_CTX] | s1[VXD_NUM_CTX] | s0[VXD_NUM_CS_CTX] | s1[VXD_NUM_CS_CTX]
+#define VXD_RW_SCRATCH  (2 * VXD_SLOT_ELEMS * 2)        // per workgroup: the level tile and scan table of the walk (what wave 0's big-block slots are to the search's estimator pass)
+struct VxCtuSynFrame { uint8_t sao_luma, sao_chroma, alf[3], n_aps /* luma parameter sets of the slice */, n_alt /* alternatives of its chroma set */, pad_; };
+struct VxSaoSyn { int8_t mode, type, band, offset[4]; };      // same layout as vvcx_sao_param: the CODED parameters (merges unresolved)
+struct VxRewriteParams {
+  const VxCtuSynFrame *hdr;       // [frame]
+  const VxSaoSyn *sao;            // [frame][ctu][3]; NULL when no frame has SAO on
+  const VxAlfCtu *alf;            // [frame][ctu]; NULL when no frame has ALF on
+  const int32_t *tile_of_ctu;     // [ctu]: the tile index, as wide as the kernel's own (a tile grid may have more than 255 tiles)
+  const int32_t *tile_sub0, *tile_nsub;      // per tile: first sub-stream and count (one, or with WPP the CTU rows)
+  const int32_t *sub_first;       // [nsub + 1]: where the CTUs of a sub-stream start in sub_ctu
+  const int32_t *sub_ctu;         // CTU raster addresses, sub-stream by sub-stream in coding order
+  const uint16_t *ctx0;           // [VXD_RW_CTX] start states of the slice
+  uint16_t *sync;                 // per workgroup [VXD_RW_CTX]: WPP, the states behind the first CTU of the row above
+  uint8_t *scratch;               // per workgroup VXD_RW_SCRATCH bytes
+  int32_t *trace;                 // per workgroup trace_cap operations {kind, a, b}; NULL: no trace
+  uint32_t *trace_n;              // per workgroup: operations the tile produced (beyond trace_cap: not stored)
+  int32_t trace_cap, pad_;
+};
+
 // per-stream scratch layout (bytes)
 #define VXD_STORE_REC   (128 * 128 * 2)
 #define VXD_STORE_UNITS (32 * 32 * (int) sizeof(VxUnit))

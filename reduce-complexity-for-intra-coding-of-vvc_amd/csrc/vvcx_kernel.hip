@@ -18,6 +18,7 @@
 #include <stdint.h>
 #define VX_QUAL static __device__ const
 #include "vvcx_tables.h"
+#include "vvcx_ctu_syntax_tables.h"
 #include "vvcx_dev.h"
 #include "vvcx_mip_dev.h"
 
@@ -392,13 +393,26 @@ __device__ __noinline__ void arith_bin(unsigned bin, unsigned st)      // TBinEn
     if (a.bits_left < 12) arith_write_out();
   }
 }
-// WR: also drive the arithmetic coder L.aw (bitstream pass only; a template so that the estimator's copies contain no call)
-template <bool WR = false>
+// State of the payload rewrite (vvcx_rewrite_kernel_*, thread 0): the 15 context models of the SAO / ALF CTU syntax (vvcx_ctu_syntax_tables.h), which stay outside L.ctxs -
+// the LDS object, its snapshots and the search kernels know nothing of them - and the operation trace of the tile.  An LDS object of its own that only the rewrite
+// kernels reach.
+struct RwState { uint16_t s0[VX_CS_NUM_CTX], s1[VX_CS_NUM_CTX]; int32_t *trace; uint32_t trace_cap, trace_n; };
+__shared__ RwState RW;
+// one operation {kind, a, b} in the format of vvcx_arith_encode; beyond the capacity it is only counted
+__device__ inline void rw_trace(int kind, int a, int b)
+{
+  if (RW.trace_n < RW.trace_cap) { int32_t *o = RW.trace + 3 * (size_t) RW.trace_n; o[0] = kind; o[1] = a; o[2] = b; }
+  RW.trace_n++;
+}
+// WR: also drive the arithmetic coder L.aw (bitstream pass only; a template so that the estimator's copies contain no call); WR == 2: the payload rewrite, which also
+// leaves every operation in its trace, context models as the reference's flat indices (a value of its own, so that the search kernels' writer carries no trace code)
+template <int WR = 0>
 __device__ inline void enc_bin(Cab &cb, unsigned bin, int ctx)
 {
   Ctx *c = &L.ctxs[cb.ci];
   const unsigned st = (unsigned) (c->s0[ctx] + c->s1[ctx]) >> 8;
   cb.bits += BIN_FRAC(st, bin);
+  if (WR == 2) rw_trace(0, (int) VX_CTX_REF_INDEX[ctx], (int) bin);
   if (WR) arith_bin(bin, st);
   const int rate = L.t.ctx_rate[ctx];
   const int r0 = 2 + ((rate >> 2) & 3), r1 = 3 + r0 + (rate & 3);
@@ -408,8 +422,8 @@ __device__ inline void enc_bin(Cab &cb, unsigned bin, int ctx)
   c->s0[ctx] = (uint16_t) a; c->s1[ctx] = (uint16_t) b;
 }
 // n bypass bins of the given value, MSB first (the estimator only needs n)
-template <bool WR = false>
-__device__ inline void enc_ep(Cab &cb, uint32_t value, int n) { cb.bits += (uint64_t) n << 15; if (WR && n > 0) arith_bins_ep(value, n); }
+template <int WR = 0>
+__device__ inline void enc_ep(Cab &cb, uint32_t value, int n) { cb.bits += (uint64_t) n << 15; if (WR == 2 && n > 0) rw_trace(1, (int) value, n); if (WR && n > 0) arith_bins_ep(value, n); }
 
 __device__ void cg_shape(int w, int h, int &lcw, int &lch)     // g_log2SbbSize, CL/Rom.cpp:250-261
 {
@@ -432,7 +446,7 @@ __device__ void diag_pos(int bw, int bh, int n, int &ox, int &oy)
   }
   ox = col; oy = line;
 }
-template <bool WR = false>
+template <int WR = 0>
 __device__ inline void enc_rem_abs(Cab &cb, unsigned bins, unsigned rice)       // EL/BinEncoder.cpp:444-472
 {
   const unsigned thr = 5u << rice;
@@ -545,7 +559,7 @@ __device__ __noinline__ RcPre rc_prepass_wave(int lev_off, const int16_t *coeff_
   r.sig_raster = ((unsigned long long) (unsigned) wave_sum_i32(rhi) << 32) | (unsigned) wave_sum_i32(rlo);
   return r;
 }
-template <bool WR = false>
+template <int WR = 0>
 __device__ __noinline__ void rc_serial(Cab &cb, const int16_t *coeff, int w, int h, int is_chroma, const uint16_t *scan, RcPre pre, int zo = 0)
 {
   Cctx c; c.w = w; c.h = h; c.ch = is_chroma; c.tmpl_diag = -1; c.tmpl_sum1 = -1;
@@ -639,7 +653,7 @@ __device__ __noinline__ void rc_serial(Cab &cb, const int16_t *coeff, int w, int
   }
 }
 // single-lane form (controller / estimator pass) and wave form (lane 0 owns cb)
-template <bool WR = false>
+template <int WR = 0>
 __device__ void residual_coding(Cab &cb, const int16_t *coeff, int w, int h, int is_chroma, uint16_t *scan, int zo = 0)
 {
   const RcPre pre = rc_prepass_serial(coeff, w, h, scan);
@@ -971,7 +985,7 @@ __device__ __noinline__ void prepare_node(const VxParams &p_, const VxFrameDev &
   f.ctx_spl = (uint8_t) ctxSpl; f.ctx_qt = (uint8_t) ctxQt; f.ctx_hv = (uint8_t) ctxHv;
 }
 // CABACWriter::split_cu_mode (EL/CABACWriter.cpp:1010-1069)
-template <bool WR = false>
+template <int WR = 0>
 __device__ void enc_split_cu_mode(const VxParams &p, const VxFrameDev &fd, Cab &cb, Frame &f, int ch, int tile, int split)
 {
   const int m = f.can_mask;
@@ -1036,7 +1050,7 @@ __device__ void derive_mpms(int Ld, int Ad, unsigned mpm[6])
 // CABACWriter::intra_luma_pred_mode 1762-1845 + extend_ref_line 1566-1591 (ISP off); MPMs from L.mpm; mip_flag 4741-4767 with the node's
 // context (DeriveCtx::CtxMipFlag) and mip_pred_mode 4781-4787 = xWriteTruncBinCode(mode, numModes) from L.mip_n / L.mip_ctx
 // isp: cu.ispMode (0 none, 1 horizontal, 2 vertical split); isp_mode (3944-3965) follows the reference line index of every luma CU that could use ISP
-template <bool WR = false>
+template <int WR = 0>
 __device__ void enc_intra_luma_pred_mode(Cab &cb, int y, int dir, int mrl, int isp = 0)
 {
   if (L.mip_n) {
@@ -1095,7 +1109,7 @@ __device__ unsigned long long luma_mode_bits(const Ctx &c, int y, int dir, int m
 }
 // CABACWriter::intra_chroma_pred_mode 1891-1933 + intra_chroma_lmc_mode 1864-1888; lm = co-located luma mode (candidate list
 // CL/UnitTools.cpp:840-873), lm_ok = CodingUnit::checkCCLMAllowed
-template <bool WR = false>
+template <int WR = 0>
 __device__ void enc_intra_chroma_pred_mode(Cab &cb, int dir, int lm, int lm_ok)
 {
   if (lm_ok) {
@@ -1694,7 +1708,7 @@ __device__ __noinline__ void lmcs_chroma_adj(int nx, int ny)
 // ------------------------------------------------------------------------------------------------ transform + quant (one wave)
 #include "vvcx_trquant_dev.h"
 // CABACWriter::mts_coding 3885-3941 for a TU where MTS is allowed and transform skip is not (JVET_O0294 contexts); lane 0 / thread 0
-template <bool WR = false>
+template <int WR = 0>
 __device__ inline void enc_mts_idx(Cab &cb, int mts)
 {
   enc_bin<WR>(cb, (unsigned) (mts != 0), VX_CTX_MTSIndex + 0);
@@ -1713,7 +1727,7 @@ __device__ inline int lfnst_flags(int last, int w, int h)
 }
 // CABACWriter::residual_lfnst_mode (3989-4100) of a CU of a separate tree (context 1); w, h: the CU in luma samples; mip: cu.mipFlag (luma);
 // non_dct2: the luma block is coded with an explicit MTS pair; flags: OR of lfnst_flags over the CU's coded blocks.  lane 0 / thread 0
-template <bool WR = false>
+template <int WR = 0>
 __device__ inline void enc_lfnst_idx(Cab &cb, int ch, int w, int h, int mip, int non_dct2, int flags, int lfnst)
 {
   if (!(L.par.tools & TOOL_LFNST)) return;
@@ -1732,7 +1746,7 @@ __device__ inline void enc_lfnst_idx(Cab &cb, int ch, int w, int h, int mip, int
 // (EL/CABACWriter.cpp:4306-4555) codes the levels in forward scan order with a budget of 2 * w * h context-coded bins.  BDPCM is off (BIN/encoder_intra.cfg).
 __device__ inline int ts_allowed(const VxParams &p, int w, int h) { return (p.tools & TOOL_TS) && w <= 32 && h <= 32; }      // TU::isTSAllowed (CL/UnitTools.cpp:4524-4546), TransformSkipLog2MaxSize 5
 // CABACWriter::mts_coding 3885-3941 of a luma TU with cbf (not an ISP one): transform_skip_flag where TU::isTSAllowed, then the MTS index where TU::isMTSAllowed
-template <bool WR = false>
+template <int WR = 0>
 __device__ inline void enc_tu_mts(Cab &cb, int w, int h, int mts)
 {
   if (ts_allowed(L.par, w, h)) enc_bin<WR>(cb, (unsigned) (mts == 1), VX_CTX_MTSIndex + 6);
@@ -1855,7 +1869,7 @@ __device__ __noinline__ int ts_rdoq_lane(int16_t *cf, int w, int h, int bd, int 
   return absSum;
 }
 // residual_codingTS + residual_coding_subblockTS (EL/CABACWriter.cpp:4306-4555, JVET_O0122 / O0409 / O0619 forms) on the estimator / writer: one thread
-template <bool WR = false>
+template <int WR = 0>
 __device__ __noinline__ void rc_ts_serial(Cab &cb, const int16_t *lv, int w, int h)
 {
   const ScanGeo g = scan_geo(w, h);
@@ -4296,7 +4310,7 @@ __device__ __attribute__((always_inline)) inline void control_step(const VxParam
 
 // final estimator pass over the coded CTU (CABACWriter::coding_tree_unit 254-309 / coding_tree 474-984): advances
 // L.ctxs[CI_CUR] for the next CTU of the stream.  Thread 0 only.
-template <typename T, bool WR>
+template <typename T, int WR>
 __device__ __noinline__ void walk_tree(const VxParams &p_, const VxFrameDev &fd_, Cab &cb, int ch, int tile, Frame *st_, int d, int16_t *lv)
 {
   const VxParams &p = L.par; (void) p_; const VxFrameDev &fd = L.fdv; (void) fd_;
@@ -4618,6 +4632,149 @@ __device__ int run_stream(const VxParams &p, int stream_idx, int pos0)
   if (tid == 0) { for (int i = 0; i < 4; i++) atomicAdd(&p.counters[i], L.cnt[i]); if (VVCX_STAMP) for (int i = 0; i < 48; i++) atomicAdd(&p.counters[4 + i], PROF(i)); }
   return pos0 + t;
 }
+
+// ------------------------------------------------------------------------------------------------ payload rewrite
+// The SAO and ALF parameters of a picture exist only after it has been searched, deblocked and analysed, but their bins lie in front of every coding tree inside each
+// tile's arithmetic codeword: the payload is written a second time.  The pass reads what persists after the search - the CU maps and level planes of the picture
+// (vvcx_get_cus / vvcx_get_levels) - and no search state; walk_tree looks at left and above neighbours only, which are coded in either pass.
+// Thread 0 of a workgroup codes one tile: nobody waits on anybody, under WPP the rows of the tile follow one another in the same workgroup.
+static_assert(VXD_NUM_CS_CTX == VX_CS_NUM_CTX, "vvcx_dev.h and vvcx_ctu_syntax_tables.h disagree on the number of CTU-syntax models");
+// a bin on model k of the CTU-syntax set: enc_bin's estimate, coder call and update rule on RW's states
+template <int WR>
+__device__ inline void cs_bin(Cab &cb, unsigned bin, int k)
+{
+  const unsigned st = (unsigned) (RW.s0[k] + RW.s1[k]) >> 8;
+  cb.bits += BIN_FRAC(st, bin);
+  if (WR == 2) rw_trace(0, (int) VX_CS_REF_INDEX[k], (int) bin);
+  if (WR) arith_bin(bin, st);
+  const int rate = VX_CS_RATE[k];
+  const int r0 = 2 + ((rate >> 2) & 3), r1 = 3 + r0 + (rate & 3);
+  unsigned a = RW.s0[k], b = RW.s1[k];
+  a -= (a >> r0) & 0x7FE0u; b -= (b >> r1) & 0x7FFEu;
+  if (bin) { a += (0x7fffu >> r0) & 0x7FE0u; b += (0x7fffu >> r1) & 0x7FFEu; }
+  RW.s0[k] = (uint16_t) a; RW.s1[k] = (uint16_t) b;
+}
+// CABACWriter::xWriteTruncBinCode (EL/CABACWriter.cpp:1528-1564)
+template <int WR>
+__device__ inline void enc_trunc_bin(Cab &cb, unsigned sym, unsigned maxSym)
+{
+  const int th = ilog2i((int) maxSym);
+  const unsigned val = 1u << th, b = maxSym - val;
+  if (sym < val - b) enc_ep<WR>(cb, sym, th); else enc_ep<WR>(cb, sym + val - b, th + 1);
+}
+// CABACWriter::sao_offset_pars (385-462) of one component; first: Y or Cb, which carry the type (and the edge class) of their channel type
+template <int WR>
+__device__ void enc_sao_offset_pars(Cab &cb, const VxSaoSyn &s, int first, int maxQ)
+{
+  if (first) {
+    cs_bin<WR>(cb, s.mode != 0, VX_CS_SaoTypeIdx);
+    if (s.mode != 0) enc_ep<WR>(cb, s.type == 4 ? 0u : 1u, 1);
+  }
+  if (s.mode != 1) return;
+  for (int i = 0; i < 4; i++) {                            // sao_offset_abs: unary_max_eqprob (4631-4653)
+    const int a = iabs((int) s.offset[i]), last = a < maxQ;
+    enc_ep<WR>(cb, ((1u << a) - 1u) << last, a + last);
+  }
+  if (s.type == 4) {
+    for (int i = 0; i < 4; i++) if (s.offset[i]) enc_ep<WR>(cb, s.offset[i] < 0, 1);      // sao_offset_sign
+    enc_ep<WR>(cb, (uint32_t) s.band, 5);                  // sao_band_position
+  } else if (first) enc_ep<WR>(cb, (uint32_t) s.type, 2);  // sao_eo_class_luma / _chroma
+}
+// what CABACWriter::coding_tree_unit (254-309) writes in front of the coding trees of a CTU: sao() 323-382, then per component codeAlfCtuEnableFlag 4700-4725 and, luma,
+// codeAlfCtuFilterIndex 4833-4892 / chroma, codeAlfCtuAlternative 4920-4943.  A neighbour counts when it lies in the tile (≙ getCURestricted on the brick map)
+template <int WR>
+__device__ __noinline__ void enc_ctu_syntax(Cab &cb, const VxRewriteParams &r, const VxCtuSynFrame &hd, int frame, int addr, int tile)
+{
+  const VxParams &p = L.par;
+  const size_t ctu0 = (size_t) frame * p.ctus_w * p.ctus_h;
+  const int left = (addr % p.ctus_w) != 0 && r.tile_of_ctu[addr - 1] == tile, above = addr >= p.ctus_w && r.tile_of_ctu[addr - p.ctus_w] == tile;
+  if (hd.sao_luma || hd.sao_chroma) {
+    const VxSaoSyn *s = r.sao + (ctu0 + addr) * 3;
+    int mergeL = 0, mergeA = 0;
+    if (left) { mergeL = s[0].mode == 2 && s[0].type == 0; cs_bin<WR>(cb, (unsigned) mergeL, VX_CS_SaoMergeFlag); }
+    if (above && !mergeL) { mergeA = s[0].mode == 2 && s[0].type == 1; cs_bin<WR>(cb, (unsigned) mergeA, VX_CS_SaoMergeFlag); }
+    if (!mergeL && !mergeA) {
+      const int maxQ = (1 << (imin(p.bit_depth, 10) - 5)) - 1;      // SampleAdaptiveOffset::getMaxOffsetQVal
+      for (int c = 0; c < 3; c++) if (c ? hd.sao_chroma : hd.sao_luma) enc_sao_offset_pars<WR>(cb, s[c], c != 2, maxQ);
+    }
+  }
+  for (int c = 0; c < 3; c++) {
+    if (!hd.alf[c]) continue;
+    const VxAlfCtu *u = r.alf + ctu0 + addr;
+    const int ctx = (left && u[-1].flag[c] ? 1 : 0) + (above && u[-p.ctus_w].flag[c] ? 1 : 0);
+    cs_bin<WR>(cb, u->flag[c] != 0, VX_CS_ctbAlfFlag + 3 * c + ctx);
+    if (!u->flag[c]) continue;
+    if (c == 0) {
+      const int set = u->set, n = hd.n_aps;
+      if (n == 0) { enc_trunc_bin<WR>(cb, (unsigned) set, 16); continue; }
+      cs_bin<WR>(cb, set == 16, VX_CS_AlfUseLatestFilt);
+      if (set == 16) continue;
+      if (n == 1) { enc_trunc_bin<WR>(cb, (unsigned) set, 16); continue; }
+      cs_bin<WR>(cb, set > 16, VX_CS_AlfUseTemporalFilt);
+      if (set < 16) enc_trunc_bin<WR>(cb, (unsigned) set, 16);
+      else if (n > 2) enc_trunc_bin<WR>(cb, (unsigned) (set - 17), (unsigned) (n - 1));      // exactly two sets: the other one, no index (JVET_O0247)
+    } else {
+      const int alt = u->alt[c - 1];
+      for (int i = 0; i < alt; i++) cs_bin<WR>(cb, 1, VX_CS_ctbAlfAlternative + c - 1);
+      if (alt < hd.n_alt - 1) cs_bin<WR>(cb, 0, VX_CS_ctbAlfAlternative + c - 1);
+    }
+  }
+}
+// the whole store - the kept models and the CTU-syntax ones - from / to a set of states in device memory (VXD_RW_CTX)
+__device__ void rw_ctx_load(const uint16_t *src)
+{
+  for (int i = 0; i < NCTX; i++) { L.ctxs[CI_CUR].s0[i] = src[i]; L.ctxs[CI_CUR].s1[i] = src[NCTX + i]; }
+  for (int i = 0; i < VX_CS_NUM_CTX; i++) { RW.s0[i] = src[2 * NCTX + i]; RW.s1[i] = src[2 * NCTX + VX_CS_NUM_CTX + i]; }
+}
+__device__ void rw_ctx_store(uint16_t *dst)
+{
+  for (int i = 0; i < NCTX; i++) { dst[i] = L.ctxs[CI_CUR].s0[i]; dst[NCTX + i] = L.ctxs[CI_CUR].s1[i]; }
+  for (int i = 0; i < VX_CS_NUM_CTX; i++) { dst[2 * NCTX + i] = RW.s0[i]; dst[2 * NCTX + VX_CS_NUM_CTX + i] = RW.s1[i]; }
+}
+template <typename T>
+__device__ void rewrite_tile(const VxParams &p, const VxRewriteParams &r)
+{
+  const int wg = (int) blockIdx.x, frame = wg / p.ntiles, tile = wg - frame * p.ntiles;
+  VX_POISON_LDS(L);
+  if (VTX == 0) { L.par = p; L.fdv = p.frames[frame]; L.cur_tile = tile; L.frame = frame; L.lmcs_cadj = 0; L.lmcs_tab = 0; }
+  load_tables();
+  __syncthreads();
+  if (VTX != 0) return;                                    // (no barrier below)
+  const VxCtuSynFrame hd = r.hdr[frame];
+  int16_t *lv = (int16_t *) (r.scratch + (size_t) wg * VXD_RW_SCRATCH);
+  uint16_t *sync = r.sync + (size_t) wg * VXD_RW_CTX;
+  RW.trace = r.trace ? r.trace + (size_t) wg * 3 * (size_t) r.trace_cap : nullptr; RW.trace_cap = r.trace ? (uint32_t) r.trace_cap : 0u; RW.trace_n = 0;
+  const int sub0 = r.tile_sub0[tile], ns = r.tile_nsub[tile];
+  for (int k = 0; k < ns; k++) {                           // the tile, or with WPP its CTU rows: each a coder run and a sub-stream of its own (EL/EncSlice.cpp:1972-1990)
+    const int sub = sub0 + k, sidx = frame * p.nsub + sub;
+    rw_ctx_load(k == 0 ? r.ctx0 : sync);                   // WPP: from the states behind the first CTU of the row above, the whole store (1648-1661, 1801-1805)
+    L.aw_out = p.payload + p.payload_off[sidx]; L.aw_cap = p.payload_cap[sidx];
+    arith_start();
+    const int c0 = r.sub_first[sub], c1 = r.sub_first[sub + 1];
+    for (int i = c0; i < c1; i++) {
+      const int addr = r.sub_ctu[i], ctu_x = (addr % p.ctus_w) << 7, ctu_y = (addr / p.ctus_w) << 7;
+      Cab cb; cb.ci = CI_CUR; cb.bits = 0;
+      enc_ctu_syntax<2>(cb, r, hd, frame, addr, tile);
+      for (int q = 0; q < 4; q++) {                        // the coding trees as advance_ctx_ctu walks them
+        const int qx = ctu_x + ((q & 1) ? 64 : 0), qy = ctu_y + ((q >= 2) ? 64 : 0);
+        if (qx >= p.pic_w || qy >= p.pic_h) continue;
+        for (int ch = 0; ch < (p.chroma ? 2 : 1); ch++) {
+          Frame &f = L.fr[1];
+          f.x = (int16_t) qx; f.y = (int16_t) qy; f.w = 64; f.h = 64; f.depth = 1; f.qt = 1; f.bt = 0; f.mt = 0; f.impl_bt = 0; f.last_split = SPLIT_QT; f.part_idx = (uint8_t) q;
+          walk_tree<T, 2>(p, L.fdv, cb, ch, tile, L.fr, 1, lv);
+        }
+      }
+      const int lastOfSub = i + 1 == c1, lastSub = sub == p.nsub - 1;      // writer_end_of_ctu, traced
+      if (!(lastOfSub && lastSub)) { rw_trace(2, 0, 0); arith_trm(0); }
+      if (lastOfSub) { rw_trace(2, 1, 0); arith_trm(1); arith_finish(); }
+      if (i == c0 && k + 1 < ns) rw_ctx_store(sync);
+    }
+    ((Arith *) p.arith_state)[sidx] = L.aw;
+  }
+  r.trace_n[wg] = RW.trace_n;
+}
+extern "C" __global__ void __launch_bounds__(NT) vvcx_rewrite_kernel_u8(VxParams p, VxRewriteParams r) { rewrite_tile<uint8_t>(p, r); }
+extern "C" __global__ void __launch_bounds__(NT) vvcx_rewrite_kernel_u16(VxParams p, VxRewriteParams r) { rewrite_tile<uint16_t>(p, r); }
 
 // ------------------------------------------------------------------------------------------------ leaf operators
 // The device functions of the path behind the individually testable operators of include/vvcx.h (≙ the reference's

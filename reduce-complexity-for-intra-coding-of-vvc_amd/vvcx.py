@@ -397,6 +397,39 @@ class VvcxEncoder:
         self._chk(self.L.vvcx_get_payload(self.h, frame, tile, buf.ctypes.data, cap, C.byref(n)))
         return buf[:n.value].copy()
 
+    def rewrite_payload(self, hdr, sao=None, alf=None, trace_ops=0):
+        """vvcx_rewrite_payload_bound_frames: every tile's payload once more, with the SAO / ALF CTU syntax in front of each coding tree.  hdr uint8 [n_frames, 5] =
+        slice_sao_luma_flag, slice_sao_chroma_flag, ALF enabled Y / Cb / Cr; sao int8 [n_frames, ctus, 3, 7] as sao_bound_frames takes it (None: SAO off); alf = one dict
+        of synth.alf_test_params' form per bound frame as alf_bound_frames takes them (None: ALF off); trace_ops > 0 keeps that many coder operations per tile for
+        payload_ops.  Returns the kernel time in ms"""
+        hdr = np.ascontiguousarray(hdr, np.uint8).reshape(self.n_frames, 5)
+        if sao is not None:
+            sao = np.ascontiguousarray(sao, np.int8).reshape(self.n_frames, self.ctus_per_frame, 3, 7)
+        aps, sl, ctu = (None, None, None)
+        if alf is not None:
+            assert len(alf) == self.n_frames
+            aps, sl, ctu = _alf_args(alf)
+        self.L.vvcx_rewrite_payload_bound_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        self._chk(self.L.vvcx_rewrite_payload_bound_frames(self.h, hdr.ctypes.data, None if sao is None else sao.ctypes.data, C.addressof(aps) if aps is not None and len(aps) else None,
+                                                           0 if aps is None else len(aps), None if sl is None else C.addressof(sl), None if ctu is None else ctu.ctypes.data,
+                                                           int(trace_ops), None))
+        return self.last_rewrite_ms()
+
+    def last_rewrite_ms(self):
+        self.L.vvcx_last_rewrite_ms.restype = C.c_float
+        self.L.vvcx_last_rewrite_ms.argtypes = [C.c_void_p]
+        return float(self.L.vvcx_last_rewrite_ms(self.h))
+
+    def payload_ops(self, frame, tile):
+        """vvcx_get_payload_ops (diagnostic): the (n, 3) int32 operations {kind, a, b} the last traced rewrite coded for the tile, in arith_encode's format with the
+        reference's flat context indices; under TOOL_WPP the CTU rows back to back, each ending with its terminating-bin operations"""
+        n = C.c_int()
+        self.L.vvcx_get_payload_ops.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        self._chk(self.L.vvcx_get_payload_ops(self.h, frame, tile, None, 0, C.byref(n)))
+        ops = np.zeros((n.value, 3), np.int32)
+        self._chk(self.L.vvcx_get_payload_ops(self.h, frame, tile, ops.ctypes.data, len(ops), C.byref(n)))
+        return ops
+
     def enable_training_dump(self, cap_rows):
         """vvcx_enable_training_dump: every qualifying luma node of the search leaves a row of 26 features + complexity class + chosen partition"""
         self.L.vvcx_enable_training_dump.argtypes = [C.c_void_p, C.c_int]
