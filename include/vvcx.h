@@ -244,7 +244,8 @@ int   vvcx_sao_picture(int pic_w, int pic_h, int bit_depth, int tile_cols, int t
  * ctus[frame][ctu raster address]: enable flags Y / Cb / Cr (≙ Picture::getAlfCtuEnableFlag), luma filter set (getAlfCtbFilterIndex), chroma alternatives
  * (getAlfCtuAlternativeData).  Class derivation (deriveClassificationBlk 792-1002), the 7 x 7 / 5 x 5 diamond filters with clipping (filterBlk 1005-1296) and the virtual
  * boundary above every lower CTU border are the reference's; tiles are not looked at (its ALF of this version does not either).  The parameter DECISION
- * (EncAdaptiveLoopFilter) is vvcx_alf_statistics_bound_frames + vvcx_alf_decide below (linear filters).  In the reference's order this follows vvcx_sao_bound_frames. */
+ * (EncAdaptiveLoopFilter) is vvcx_alf_statistics_bound_frames + vvcx_alf_decide below (linear filters), or vvcx_alf_statistics_resident + vvcx_alf_decide_resident
+ * (statistics kept in device memory; nonlinear filters and the fixed sets as candidates).  In the reference's order this follows vvcx_sao_bound_frames. */
 typedef struct vvcx_alf_aps {
   int32_t num_luma_filters; uint8_t class_to_filter[25]; uint8_t nonlinear_luma; int16_t luma_coeff[25][12]; uint8_t luma_clip_idx[25][12];
   int32_t num_chroma_alt; uint8_t nonlinear_chroma[8]; int16_t chroma_coeff[8][6]; uint8_t chroma_clip_idx[8][6];
@@ -291,10 +292,63 @@ float vvcx_last_alf_stats_ms(const vvcx_handle *h);
  * Bits (this project's own count of the syntax, not the reference's estimator): parameter set luma = 1 (clip flag) + ue(filters - 1) + 25 * ceil(log2 filters) when there
  * are several + per coefficient ue(|c|) + 1 sign bit when c != 0; chroma = 1 + ue(0) + the coefficients; an enabled luma CTU costs one bin more than a disabled one
  * (alf_use_aps_flag), a chroma CTU's flag costs the same either way; a component whose gain does not pay for its parameter-set bits stays unfiltered.
- * Out of scope: the clip-index search for nonlinear filters (a caller's encoder can run it from the 4-bin statistics), the fixed filter sets as candidates, several chroma
- * alternatives, parameter-set reuse across pictures.  Parity with the reference's RD choice is unpinned (the unit does not compile in this environment). */
+ * Not here: the clip-index search for nonlinear filters and the fixed filter sets as candidates (vvcx_alf_decide_resident / vvcx_alf_decide_picture below have both);
+ * out of scope: several chroma alternatives, parameter-set reuse across pictures.  Parity with the reference's RD choice is unpinned (the unit does not compile in this environment). */
 int   vvcx_alf_decide(int pic_w, int pic_h, int bit_depth, int chroma, int n_bins, const int64_t *luma, const int64_t *chroma_stats,
                       const double lambda[3], int max_luma_filters, vvcx_alf_aps *aps, vvcx_alf_slice *slice, vvcx_alf_ctu *ctus);
+/* ---- the decision from statistics that STAY in device memory, with nonlinear filters and the fixed filter sets (csrc/vvcx_alf_eval.hip).  Call order on bound pictures:
+ *   ... -> vvcx_sao_bound_frames -> vvcx_alf_statistics_resident -> vvcx_alf_decide_resident -> vvcx_alf_bound_frames
+ * (vvcx_alf_bound_frames takes at most 8 parameter sets per call and vvcx_alf_decide_resident fills one per frame: a caller with more bound frames than that filters them
+ * in groups of pictures that share their sets.)  What the decision needs from the 550 KB of a CTU are two things, both device passes:
+ *   the masked frame sums (≙ getFrameStats, EL/EncAdaptiveLoopFilter.cpp:2491-2565): per frame and class the sum of the blocks of the CTUs whose mask byte is set;
+ *   the candidate errors (≙ calcErrorForCoeffs, EL 225-242, per CTU and filter set as alfEncoderCtb 3153-3300 asks for them): per (CTU, candidate set s)
+ *     err[s] = sum over classes ( sum_{k,l < 12} q_k q_l E[clip_k][clip_l][k][l]  -  256 sum_k q_k y[clip_k][k] )      (chroma: one class, 6 taps; the centre row is not used)
+ *   with q / clip the candidate's filter of the class; err / 16384 + pixAcc is the squared error the set is predicted to leave on the CTU.  err is EXACT in int64:
+ *   |v| < 2^(bd+1), at most 2^14 samples per CTU, |q| <= 128, 144 terms, so |quadratic term| < 2^(2 bd + 37.2): 2^57.2 at 10 bit, 2^61.2 at 12 bit (a double would round
+ *   it).  Coefficients beyond +-128 and clipping indices >= the gathered bin count are refused (VVCX_ERR_ARG).  With fixed_sets the candidates 0..15 are the standard's
+ *   fixed filter sets (clipping index 0), the caller's follow; at most 64 candidates per component and call.
+ * vvcx_alf_statistics_resident: vvcx_alf_statistics_bound_frames without the copy to the host; the handle remembers (frame range, bins, chroma).  Every call that binds,
+ * compresses or filters the bound pictures (and vvcx_alf_statistics_bound_frames, which uses the same memory) makes them stale: the three calls below then return
+ * VVCX_ERR_STATE, as they do when nothing was gathered.  ctu_on = [n][ctus][3] bytes (Y, Cb, Cr; NULL: every CTU); luma = [n][25][size], chroma = [n][2][size] (sizes
+ * as for the statistics; chroma may be NULL); candidates are given per frame: luma_cands[n][n_luma], chroma_cands[n][n_chroma]; luma_err = [n][ctus][16 fixed_sets +
+ * n_luma], chroma_err = [n][ctus][2][n_chroma].  All of these are host memory; the calls block until their results have arrived. */
+typedef struct vvcx_alf_luma_cand { int16_t coeff[25][12]; uint8_t clip_idx[25][12]; } vvcx_alf_luma_cand;      /* per class, class_to_filter applied */
+typedef struct vvcx_alf_chroma_cand { int16_t coeff[6]; uint8_t clip_idx[6]; } vvcx_alf_chroma_cand;
+int   vvcx_alf_statistics_resident(vvcx_handle *h, int frame_first, int n, int n_bins, void *hip_stream);
+int   vvcx_alf_frame_statistics(vvcx_handle *h, const uint8_t *ctu_on, int64_t *luma, int64_t *chroma, void *hip_stream);
+int   vvcx_alf_candidate_errors(vvcx_handle *h, int fixed_sets, const vvcx_alf_luma_cand *luma_cands, int n_luma, const vvcx_alf_chroma_cand *chroma_cands, int n_chroma,
+                                int64_t *luma_err, int64_t *chroma_err, void *hip_stream);
+float vvcx_last_alf_sum_ms(const vvcx_handle *h);       /* the kernel of the last frame sums / candidate errors of the handle (the decision's last ones included) */
+float vvcx_last_alf_cand_ms(const vvcx_handle *h);
+/* The decision of every resident frame; only frame sums and error tables cross to the host.  Per frame i it fills aps[i], slices[i] and ctus[i][ctu] exactly in
+ * vvcx_alf_decide's layout (luma_aps = {0} and chroma_aps = 0 refer to aps[i]).  flags = 0: vvcx_alf_decide's result on the same statistics (the per-CTU comparisons
+ * read the device's exact errors, so this holds wherever none of them is a tie at double precision).  The flags add candidates; parity with the reference's RD choice
+ * is unpinned, as for vvcx_alf_decide.
+ * VVCX_ALF_NONLINEAR_LUMA / _CHROMA (4 bins must have been gathered, else VVCX_ERR_ARG): per filter group, from the linear solution with clipping index 0, a greedy
+ *   search in the manner of AlfCovariance::optimizeFilter (EL 88-223): with step 2, then 1, per tap clip +- step on the gathered E[clip_k][clip_l][k][l], y[clip_k][k],
+ *   re-solved; the best improving move is taken until none improves; then the rounding and single-step refinement of vvcx_alf_decide on the gathered matrix (kept only
+ *   when it predicts less than the linear filter); then every index whose lower neighbour has identical rows, or whose coefficient is 0, is lowered (≙ reduceClipCost,
+ *   EL 68-86).  The nonlinear flag is set only if an index stays non-zero and the gain pays for the clip bits: 2 bits per tap of every filter once the flag is on (this
+ *   project's own count).  Merging keeps using bin 0 (the reference re-optimises the clips inside mergeClasses, EL 2344-2490).
+ * VVCX_ALF_FIXED_SETS: per CTU the least of off, fixed set 0..15 (1 bin + 4 bypass bits, as codeAlfCtuFilterIndex writes them, EL/CABACWriter.cpp:4833-4892) and the new
+ *   set (1 bin); the new set is derived once more from the CTUs that chose it and evaluated a last time; if its gain over the best choice without it does not pay for
+ *   its parameter-set bits the slice carries no luma set (n_luma_aps = 0, CTU sets < 16).
+ * With J = sum over CTUs (predicted error + lambda * bits) + lambda * parameter-set bits, the returned decision has by construction J <= J(all off), J <= J(the flags-0
+ * decision) and, with VVCX_ALF_FIXED_SETS, J <= J(the best choice among off and the fixed sets): it is the least of these complete decisions and the new-set ones.
+ * Out of scope: several chroma alternatives, parameter-set reuse across pictures, parity with EncAdaptiveLoopFilter's RD choice. */
+#define VVCX_ALF_NONLINEAR_LUMA   1
+#define VVCX_ALF_NONLINEAR_CHROMA 2
+#define VVCX_ALF_FIXED_SETS       4
+int   vvcx_alf_decide_resident(vvcx_handle *h, const double lambda[3], int max_luma_filters, int flags, vvcx_alf_aps *aps, vvcx_alf_slice *slices, vvcx_alf_ctu *ctus,
+                               void *hip_stream);
+/* the host-plane forms (no handle; org / rec as for vvcx_alf_statistics_picture, chroma planes required): the planes are uploaded, the statistics gathered into temporary
+ * device memory, and the same kernels and the same decision code run.  vvcx_alf_evaluate_picture: ctu_on[ctus][3] (may be NULL) -> luma_sum[25][size], chroma_sum[2][size];
+ * the candidates -> luma_err[ctus][16 fixed_sets + n_luma], chroma_err[ctus][2][n_chroma] (either pair of outputs may be NULL).  Parity unpinned, as above. */
+int   vvcx_alf_evaluate_picture(int pic_w, int pic_h, int bit_depth, int n_bins, const uint16_t *const org[3], const uint16_t *const rec[3], const uint8_t *ctu_on,
+                                int fixed_sets, const vvcx_alf_luma_cand *luma_cands, int n_luma, const vvcx_alf_chroma_cand *chroma_cands, int n_chroma,
+                                int64_t *luma_sum, int64_t *chroma_sum, int64_t *luma_err, int64_t *chroma_err, int device);
+int   vvcx_alf_decide_picture(int pic_w, int pic_h, int bit_depth, int n_bins, const uint16_t *const org[3], const uint16_t *const rec[3], const double lambda[3],
+                              int max_luma_filters, int flags, vvcx_alf_aps *aps, vvcx_alf_slice *slice, vvcx_alf_ctu *ctus, int device);
 /* ≙ LoopFilter::loopFilterPic on a picture the caller describes itself (the way the reference's LoopFilter sees a CodingStructure: cs.cus + cs.tus + the reconstruction buffer):
  * rows = n_rows x {channel type (0 luma tree, 1 chroma tree), x, y, w, h in luma samples, cu.ispMode (0, 1 = horizontal, 2 = vertical split; luma rows only)} covering both
  * trees of the whole 4:2:0 picture, every CU intra at the slice QP (qp_cb / qp_cr = mapped chroma QPs); y / cb / cr = host planes of 16-bit samples, stride = plane width,

@@ -49,6 +49,8 @@ extern "C" __global__ void vvcx_alf_stats_b1_kernel_u8(VxAlfStatParams p);
 extern "C" __global__ void vvcx_alf_stats_b4_kernel_u8(VxAlfStatParams p);
 extern "C" __global__ void vvcx_alf_stats_b1_kernel_u16(VxAlfStatParams p);
 extern "C" __global__ void vvcx_alf_stats_b4_kernel_u16(VxAlfStatParams p);
+extern "C" __global__ void vvcx_alf_sum_kernel(VxAlfSumParams p);
+extern "C" __global__ void vvcx_alf_cand_kernel(VxAlfCandParams p);
 extern "C" __global__ void vvcx_deblock_edges_kernel(VxDeblockParams p);
 extern "C" __global__ void vvcx_deblock_kernel_u8(VxDeblockParams p);
 extern "C" __global__ void vvcx_deblock_kernel_u16(VxDeblockParams p);
@@ -73,6 +75,9 @@ static int fail(int code, const char *fmt, ...)
   va_list ap; va_start(ap, fmt); vsnprintf(g_err, sizeof g_err, fmt, ap); va_end(ap);
   return code;
 }
+
+// device buffers of the ALF decision passes (vvcx_alf_eval.hip): frame sums, error tables, the CTU mask and the candidates of a call
+struct AlfWork { DevBuf<long long> sum_l, sum_c, err_l, err_c; DevBuf<uint8_t> mask; DevBuf<VxAlfLumaCand> lc; DevBuf<VxAlfChromaCand> cc; };
 
 struct vvcx_handle {
   vvcx_cfg cfg; vvcx_slice sl; bool have_slice;
@@ -110,6 +115,8 @@ struct vvcx_handle {
   DevBuf<long long> sao_stat_d; float last_sao_stats_ms;      // vvcx_sao_statistics_bound_frames
   DevBuf<VxAlfFrame> alf_tab_d; DevBuf<VxAlfCtu> alf_ctu_d; float last_alf_ms;      // vvcx_alf_bound_frames: per-frame tables and per-CTU choices (the picture copy is the SAO one)
   DevBuf<long long> alf_stat_luma_d, alf_stat_chroma_d; float last_alf_stats_ms;      // vvcx_alf_statistics_bound_frames
+  // vvcx_alf_statistics_resident: what alf_stat_*_d hold (frame range, bins, chroma) while no call has touched the pictures since; the decision passes' buffers
+  bool alf_res_valid, alf_res_chroma; int alf_res_first, alf_res_n, alf_res_bins; AlfWork alf_work; float last_alf_sum_ms, last_alf_cand_ms;
   // vvcx_rewrite_payload_bound_frames: per-frame header flags, coded SAO parameters, ALF choices, the tile / sub-stream tables, start states, per-workgroup sync states,
   // walk scratch and operation trace; the host copy of the last trace counts
   DevBuf<VxCtuSynFrame> rw_hdr_d; DevBuf<VxSaoSyn> rw_sao_d; DevBuf<VxAlfCtu> rw_alf_d; DevBuf<uint8_t> rw_scratch_d; DevBuf<int32_t> rw_tab_d, rw_trace_d;
@@ -400,6 +407,7 @@ static void ctx_from_reference_order(const uint16_t *s0, const uint16_t *s1, uin
 extern "C" int vvcx_bind_frames(vvcx_handle *h, const vvcx_frame *frames, int n)
 {
   NOT_PENDING(h);
+  if (h) h->alf_res_valid = false;      // the resident ALF statistics no longer describe the bound pictures
   if (!h || !frames) return fail(VVCX_ERR_ARG, "null argument");
   ON_DEVICE(h->cfg.device);
   if (n < 1 || n > h->cfg.max_frames) return fail(VVCX_ERR_ARG, "n_frames %d outside 1..%d", n, h->cfg.max_frames);
@@ -515,6 +523,7 @@ static void stream_params(vvcx_handle *h, VxParams &p)
 extern "C" int vvcx_submit_ctus(vvcx_handle *h, const vvcx_ctu_task *tasks, int n, void *hip_stream)
 {
   NOT_PENDING(h);
+  if (h) h->alf_res_valid = false;      // the resident ALF statistics no longer describe the bound pictures
   if (h && (h->cfg.tools & VVCX_TOOL_FAST) && !h->f_ntrees) return fail(VVCX_ERR_STATE, "VVCX_TOOL_FAST needs vvcx_set_forest before the first CTU");
   if (!h || (!tasks && n) || n < 0) return fail(VVCX_ERR_ARG, "bad argument");
   if (n == 0) { h->pending = true; h->pend_n = 0; h->pend_stream = (hipStream_t) hip_stream; h->pend_src.clear(); h->pend_next = h->next_idx; return VVCX_OK; }   // nothing to code: an empty submission, not an error
@@ -733,6 +742,7 @@ static int require_all_coded(const vvcx_handle *h, const char *what)
 extern "C" int vvcx_lmcs_inverse_reco(vvcx_handle *h, void *hip_stream)
 {
   NOT_PENDING(h);
+  if (h) h->alf_res_valid = false;      // the resident ALF statistics no longer describe the bound pictures
   if (!h) return fail(VVCX_ERR_ARG, "null handle");
   if (!h->n_frames || !h->have_slice || !h->lmcs_on) return fail(VVCX_ERR_STATE, "no bound frames coded with an LMCS slice");
   if (!h->lmcs_lut_d.p) return fail(VVCX_ERR_STATE, "the bound pictures were not prepared with an LMCS slice: vvcx_bind_frames after vvcx_set_slice");
@@ -757,6 +767,7 @@ extern "C" int vvcx_lmcs_inverse_reco(vvcx_handle *h, void *hip_stream)
 extern "C" int vvcx_deblock_bound_frames(vvcx_handle *h, int beta_offset_div2, int tc_offset_div2, void *hip_stream)
 {
   NOT_PENDING(h);
+  if (h) h->alf_res_valid = false;      // the resident ALF statistics no longer describe the bound pictures
   if (!h) return fail(VVCX_ERR_ARG, "null handle");
   if (!h->n_frames || !h->have_slice) return fail(VVCX_ERR_STATE, "no bound frames / slice");
   if (const int rc = require_all_coded(h, "deblocking")) return rc;
@@ -853,6 +864,7 @@ static void sao_launch(VxSaoParams &p, int n_frames, size_t bps, hipStream_t str
 extern "C" int vvcx_sao_bound_frames(vvcx_handle *h, const vvcx_sao_param *prm, int lf_across_tiles, int log2_offset_scale, void *hip_stream)
 {
   NOT_PENDING(h);
+  if (h) h->alf_res_valid = false;      // the resident ALF statistics no longer describe the bound pictures
   if (!h || !prm) return fail(VVCX_ERR_ARG, "null argument");
   if (!h->n_frames || !h->have_slice) return fail(VVCX_ERR_STATE, "no bound frames / slice");
   if (log2_offset_scale < 0 || log2_offset_scale > 4) return fail(VVCX_ERR_ARG, "log2 offset scale outside 0..4");
@@ -1235,6 +1247,7 @@ static void alf_launch(VxAlfParams &p, int n_frames, size_t bps, hipStream_t str
 extern "C" int vvcx_alf_bound_frames(vvcx_handle *h, const vvcx_alf_aps *aps, int n_aps, const vvcx_alf_slice *slices, const vvcx_alf_ctu *ctus, void *hip_stream)
 {
   NOT_PENDING(h);
+  if (h) h->alf_res_valid = false;      // the resident ALF statistics no longer describe the bound pictures
   if (!h || !slices || !ctus || (n_aps > 0 && !aps)) return fail(VVCX_ERR_ARG, "null argument");
   if (!h->n_frames || !h->have_slice) return fail(VVCX_ERR_STATE, "no bound frames / slice");
   if (const int rc = require_all_coded(h, "ALF")) return rc;
@@ -1300,16 +1313,12 @@ static void alf_stats_launch(VxAlfStatParams &p, int n_frames, int nb, size_t bp
   if (bps == 1) { if (nb == 1) hipLaunchKernelGGL(vvcx_alf_stats_b1_kernel_u8, grid, dim3(256), 0, stream, p); else hipLaunchKernelGGL(vvcx_alf_stats_b4_kernel_u8, grid, dim3(256), 0, stream, p); }
   else { if (nb == 1) hipLaunchKernelGGL(vvcx_alf_stats_b1_kernel_u16, grid, dim3(256), 0, stream, p); else hipLaunchKernelGGL(vvcx_alf_stats_b4_kernel_u16, grid, dim3(256), 0, stream, p); }
 }
-extern "C" int vvcx_alf_statistics_picture(int pic_w, int pic_h, int bit_depth, int n_bins, const uint16_t *const org[3], const uint16_t *const rec[3],
-                                           int64_t *luma, int64_t *chroma, int device)
+// one picture in host memory -> its statistics in luma_d / chroma_d (the caller's device is current); the checks of the host-plane entries
+static int alf_stats_of_planes(int pic_w, int pic_h, int bit_depth, int n_bins, const uint16_t *const org[3], const uint16_t *const rec[3], bool chroma,
+                               DevBuf<long long> &luma_d, DevBuf<long long> &chroma_d)
 {
-  if (!org || !rec || !luma) return fail(VVCX_ERR_ARG, "null argument");
-  for (int c = 0; c < 3; c++) if (!org[c] || !rec[c]) return fail(VVCX_ERR_ARG, "null plane");
-  if (pic_w < 8 || pic_h < 8 || (pic_w & 7) || (pic_h & 7) || pic_w > 16384 || pic_h > 16384 || bit_depth < 8 || bit_depth > 12) return fail(VVCX_ERR_ARG, "vvcx_alf_statistics_picture: picture size / bit depth");
-  if (n_bins != 1 && n_bins != 4) return fail(VVCX_ERR_ARG, "vvcx_alf_statistics_picture: %d clipping bins (1 or 4)", n_bins);
   const int cw = (pic_w + 127) / 128, chh = (pic_h + 127) / 128, nctu = cw * chh;
-  ON_DEVICE(device);
-  DevBuf<uint16_t> planes; DevBuf<VxFrameDev> frame; DevBuf<long long> luma_d, chroma_d;
+  DevBuf<uint16_t> planes; DevBuf<VxFrameDev> frame;
   const size_t ny = (size_t) pic_w * pic_h, ncs = ny >> 2, per = ny + 2 * ncs;
   const size_t nl = (size_t) nctu * 25 * alf_stat_size(n_bins, 13), nch = (size_t) nctu * 2 * alf_stat_size(n_bins, 7);
   HIPCHK(planes.alloc(2 * per)); HIPCHK(frame.alloc(1)); HIPCHK(luma_d.alloc(nl));
@@ -1327,24 +1336,40 @@ extern "C" int vvcx_alf_statistics_picture(int pic_w, int pic_h, int bit_depth, 
   p.pic_w = pic_w; p.pic_h = pic_h; p.ctus_w = cw; p.ctus_h = chh; p.bit_depth = bit_depth;
   alf_stats_launch(p, 1, n_bins, 2, 0);
   HIPCHK(hipGetLastError()); HIPCHK(hipDeviceSynchronize());
+  return VVCX_OK;
+}
+static int alf_picture_args(const char *who, int pic_w, int pic_h, int bit_depth, int n_bins, const uint16_t *const org[3], const uint16_t *const rec[3])
+{
+  if (!org || !rec) return fail(VVCX_ERR_ARG, "null argument");
+  for (int c = 0; c < 3; c++) if (!org[c] || !rec[c]) return fail(VVCX_ERR_ARG, "null plane");
+  if (pic_w < 8 || pic_h < 8 || (pic_w & 7) || (pic_h & 7) || pic_w > 16384 || pic_h > 16384 || bit_depth < 8 || bit_depth > 12) return fail(VVCX_ERR_ARG, "%s: picture size / bit depth", who);
+  if (n_bins != 1 && n_bins != 4) return fail(VVCX_ERR_ARG, "%s: %d clipping bins (1 or 4)", who, n_bins);
+  return VVCX_OK;
+}
+extern "C" int vvcx_alf_statistics_picture(int pic_w, int pic_h, int bit_depth, int n_bins, const uint16_t *const org[3], const uint16_t *const rec[3],
+                                           int64_t *luma, int64_t *chroma, int device)
+{
+  if (!luma) return fail(VVCX_ERR_ARG, "null argument");
+  if (const int rc = alf_picture_args("vvcx_alf_statistics_picture", pic_w, pic_h, bit_depth, n_bins, org, rec)) return rc;
+  const int nctu = ((pic_w + 127) / 128) * ((pic_h + 127) / 128);
+  const size_t nl = (size_t) nctu * 25 * alf_stat_size(n_bins, 13), nch = (size_t) nctu * 2 * alf_stat_size(n_bins, 7);
+  ON_DEVICE(device);
+  DevBuf<long long> luma_d, chroma_d;
+  if (const int rc = alf_stats_of_planes(pic_w, pic_h, bit_depth, n_bins, org, rec, chroma != nullptr, luma_d, chroma_d)) return rc;
   HIPCHK(hipMemcpy(luma, luma_d.p, nl * sizeof(long long), hipMemcpyDeviceToHost));
   if (chroma) HIPCHK(hipMemcpy(chroma, chroma_d.p, nch * sizeof(long long), hipMemcpyDeviceToHost));
   return VVCX_OK;
 }
-extern "C" int vvcx_alf_statistics_bound_frames(vvcx_handle *h, int frame_first, int n, int n_bins, int64_t *luma, int64_t *chroma, void *hip_stream)
+// the checks and the launch of the two bound forms: the statistics of frames frame_first .. in alf_stat_*_d when `stream` gets there (ev0 .. ev1 around the kernel)
+static int alf_stats_bound(vvcx_handle *h, const char *who, int frame_first, int n, int n_bins, bool wantC, hipStream_t stream)
 {
-  NOT_PENDING(h);
-  if (!h || !luma) return fail(VVCX_ERR_ARG, "null argument");
   if (!h->n_frames || !h->have_slice) return fail(VVCX_ERR_STATE, "no bound frames / slice");
-  if (n_bins != 1 && n_bins != 4) return fail(VVCX_ERR_ARG, "vvcx_alf_statistics_bound_frames: %d clipping bins (1 or 4)", n_bins);
-  if (frame_first < 0 || n < 1 || frame_first > h->n_frames - n) return fail(VVCX_ERR_ARG, "vvcx_alf_statistics_bound_frames: frames %d .. %d of %d", frame_first, frame_first + n - 1, h->n_frames);
+  if (n_bins != 1 && n_bins != 4) return fail(VVCX_ERR_ARG, "%s: %d clipping bins (1 or 4)", who, n_bins);
+  if (frame_first < 0 || n < 1 || frame_first > h->n_frames - n) return fail(VVCX_ERR_ARG, "%s: frames %d .. %d of %d", who, frame_first, frame_first + n - 1, h->n_frames);
   if (h->lmcs_on) return fail(VVCX_ERR_UNSUPPORTED, "ALF statistics of an LMCS slice: the handle keeps the mapped original only");
   if (const int rc = require_all_coded(h, "the ALF statistics")) return rc;
   const int nctu = h->ctus_w * h->ctus_h;
   const size_t nl = (size_t) n * nctu * 25 * alf_stat_size(n_bins, 13), nch = (size_t) n * nctu * 2 * alf_stat_size(n_bins, 7);
-  const bool wantC = chroma && h->cfg.chroma;
-  ON_DEVICE(h->cfg.device);
-  hipStream_t stream = (hipStream_t) hip_stream;
   HIPCHK(h->alf_stat_luma_d.reserve(nl));
   if (wantC) HIPCHK(h->alf_stat_chroma_d.reserve(nch));
   VxAlfStatParams p; memset(&p, 0, sizeof p);
@@ -1354,11 +1379,38 @@ extern "C" int vvcx_alf_statistics_bound_frames(vvcx_handle *h, int frame_first,
   alf_stats_launch(p, n, n_bins, h->cfg.bit_depth == 8 ? 1 : 2, stream);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(h->ev1, stream));
+  return VVCX_OK;
+}
+extern "C" int vvcx_alf_statistics_bound_frames(vvcx_handle *h, int frame_first, int n, int n_bins, int64_t *luma, int64_t *chroma, void *hip_stream)
+{
+  NOT_PENDING(h);
+  if (h) h->alf_res_valid = false;      // the resident ALF statistics no longer describe the bound pictures
+  if (!h || !luma) return fail(VVCX_ERR_ARG, "null argument");
+  const bool wantC = chroma && h->cfg.chroma;
+  ON_DEVICE(h->cfg.device);
+  hipStream_t stream = (hipStream_t) hip_stream;
+  if (const int rc = alf_stats_bound(h, "vvcx_alf_statistics_bound_frames", frame_first, n, n_bins, wantC, stream)) return rc;
+  const int nctu = h->ctus_w * h->ctus_h;
+  const size_t nl = (size_t) n * nctu * 25 * alf_stat_size(n_bins, 13), nch = (size_t) n * nctu * 2 * alf_stat_size(n_bins, 7);
   HIPCHK(hipMemcpyAsync(luma, h->alf_stat_luma_d.p, nl * sizeof(long long), hipMemcpyDeviceToHost, stream));
   if (wantC) HIPCHK(hipMemcpyAsync(chroma, h->alf_stat_chroma_d.p, nch * sizeof(long long), hipMemcpyDeviceToHost, stream));
   HIPCHK(hipStreamSynchronize(stream));
   HIPCHK(hipEventElapsedTime(&h->last_alf_stats_ms, h->ev0, h->ev1));
   if (chroma && !wantC) memset(chroma, 0, nch * sizeof(int64_t));      // a handle without chroma
+  return VVCX_OK;
+}
+// the same without the copy: the statistics stay in device memory for vvcx_alf_frame_statistics / _candidate_errors / _decide_resident until a call touches the pictures
+extern "C" int vvcx_alf_statistics_resident(vvcx_handle *h, int frame_first, int n, int n_bins, void *hip_stream)
+{
+  NOT_PENDING(h);
+  if (!h) return fail(VVCX_ERR_ARG, "null handle");
+  h->alf_res_valid = false;
+  ON_DEVICE(h->cfg.device);
+  hipStream_t stream = (hipStream_t) hip_stream;
+  if (const int rc = alf_stats_bound(h, "vvcx_alf_statistics_resident", frame_first, n, n_bins, h->cfg.chroma != 0, stream)) return rc;
+  HIPCHK(hipStreamSynchronize(stream));
+  HIPCHK(hipEventElapsedTime(&h->last_alf_stats_ms, h->ev0, h->ev1));
+  h->alf_res_valid = true; h->alf_res_chroma = h->cfg.chroma != 0; h->alf_res_first = frame_first; h->alf_res_n = n; h->alf_res_bins = n_bins;
   return VVCX_OK;
 }
 extern "C" float vvcx_last_alf_stats_ms(const vvcx_handle *h) { return h ? h->last_alf_stats_ms : 0.f; }
@@ -1538,6 +1590,396 @@ extern "C" int vvcx_alf_decide(int pic_w, int pic_h, int bit_depth, int chroma, 
     }
   }
   return VVCX_OK;
+}
+
+// ---- the decision from statistics that stay in device memory (vvcx_alf_eval.hip): masked frame sums and per-CTU candidate errors are the only things that cross to the
+// host; with them the code above (AlfCov, alf_solve, alf_quant, alf_derive_luma) sees the inputs it would have built from downloaded statistics - the sums are exact
+// integers, and doubles of them are exact below 2^53.  include/vvcx.h says what the flags add and how the bits are counted.
+static_assert(sizeof(VxAlfLumaCand) == sizeof(vvcx_alf_luma_cand) && sizeof(VxAlfChromaCand) == sizeof(vvcx_alf_chroma_cand), "device copies of the C-ABI records");
+namespace {
+// statistics of n frames in device memory (chroma NULL: none) and where the passes put their results; ev0 / ev1 (optional) time the kernel of the last call
+struct AlfRes { const long long *luma, *chroma; int n, nctu, nb; AlfWork *w; hipStream_t stream; hipEvent_t ev0, ev1; float sum_ms, cand_ms; };
+
+static int alf_sums(AlfRes &r, const uint8_t *ctu_on, int64_t *luma, int64_t *chroma)
+{
+  const size_t szl = alf_stat_size(r.nb, 13), szc = alf_stat_size(r.nb, 7), nl = (size_t) r.n * 25 * szl, nch = (size_t) r.n * 2 * szc;
+  const bool wantC = chroma && r.chroma;
+  AlfWork &w = *r.w;
+  HIPCHK(w.sum_l.reserve(nl));
+  if (wantC) HIPCHK(w.sum_c.reserve(nch));
+  if (ctu_on) {
+    HIPCHK(w.mask.reserve((size_t) r.n * r.nctu * 3));
+    HIPCHK(hipMemcpyAsync(w.mask.p, ctu_on, (size_t) r.n * r.nctu * 3, hipMemcpyHostToDevice, r.stream));
+  }
+  VxAlfSumParams p; memset(&p, 0, sizeof p);
+  p.luma = r.luma; p.chroma = wantC ? r.chroma : nullptr; p.ctu_on = ctu_on ? w.mask.p : nullptr; p.luma_out = w.sum_l.p; p.chroma_out = wantC ? w.sum_c.p : nullptr;
+  p.nctu = r.nctu; p.size_l = szl; p.size_c = szc;
+  const dim3 grid((unsigned) ((25 * szl + 255) / 256), wantC ? 2u : 1u, (unsigned) r.n);      // one thread owns one element of the output (25 size_l >= 2 size_c)
+  if (r.ev0) HIPCHK(hipEventRecord(r.ev0, r.stream));
+  hipLaunchKernelGGL(vvcx_alf_sum_kernel, grid, dim3(256), 0, r.stream, p);
+  HIPCHK(hipGetLastError());
+  if (r.ev0) HIPCHK(hipEventRecord(r.ev1, r.stream));
+  HIPCHK(hipMemcpyAsync(luma, w.sum_l.p, nl * sizeof(long long), hipMemcpyDeviceToHost, r.stream));
+  if (wantC) HIPCHK(hipMemcpyAsync(chroma, w.sum_c.p, nch * sizeof(long long), hipMemcpyDeviceToHost, r.stream));
+  HIPCHK(hipStreamSynchronize(r.stream));
+  if (r.ev0) HIPCHK(hipEventElapsedTime(&r.sum_ms, r.ev0, r.ev1));
+  if (chroma && !wantC) memset(chroma, 0, nch * sizeof(int64_t));
+  return VVCX_OK;
+}
+
+static int alf_errors(AlfRes &r, int fixed_sets, const vvcx_alf_luma_cand *lc, int n_luma, const vvcx_alf_chroma_cand *cc, int n_chroma, int64_t *luma_err, int64_t *chroma_err)
+{
+  if (fixed_sets < 0 || fixed_sets > 1 || n_luma < 0 || n_chroma < 0 || 16 * fixed_sets + n_luma > VX_ALF_MAX_CAND || n_chroma > VX_ALF_MAX_CAND)
+    return fail(VVCX_ERR_ARG, "ALF candidates: fixed_sets %d, %d luma, %d chroma (at most %d per component, the fixed sets included)", fixed_sets, n_luma, n_chroma, VX_ALF_MAX_CAND);
+  const int ncl = 16 * fixed_sets + n_luma;
+  if (!ncl && !n_chroma) return fail(VVCX_ERR_ARG, "ALF candidates: none given");
+  if ((n_luma && !lc) || (ncl && !luma_err) || (n_chroma && (!cc || !chroma_err))) return fail(VVCX_ERR_ARG, "null argument");
+  for (size_t i = 0; i < (size_t) r.n * n_luma; i++) for (int c = 0; c < 25; c++) for (int k = 0; k < 12; k++)
+    if (lc[i].coeff[c][k] < -128 || lc[i].coeff[c][k] > 128 || lc[i].clip_idx[c][k] >= r.nb)
+      return fail(VVCX_ERR_ARG, "ALF luma candidate %d: coefficient %d / clipping index %d (|q| <= 128, index < %d gathered bins)", (int) i, lc[i].coeff[c][k], lc[i].clip_idx[c][k], r.nb);
+  for (size_t i = 0; i < (size_t) r.n * n_chroma; i++) for (int k = 0; k < 6; k++)
+    if (cc[i].coeff[k] < -128 || cc[i].coeff[k] > 128 || cc[i].clip_idx[k] >= r.nb)
+      return fail(VVCX_ERR_ARG, "ALF chroma candidate %d: coefficient %d / clipping index %d (|q| <= 128, index < %d gathered bins)", (int) i, cc[i].coeff[k], cc[i].clip_idx[k], r.nb);
+  const bool wantC = n_chroma && r.chroma;
+  const size_t nle = (size_t) r.n * r.nctu * ncl, nce = (size_t) r.n * r.nctu * 2 * n_chroma;
+  AlfWork &w = *r.w;
+  if (ncl) HIPCHK(w.err_l.reserve(nle));
+  if (n_luma) { HIPCHK(w.lc.reserve((size_t) r.n * n_luma)); HIPCHK(hipMemcpyAsync(w.lc.p, lc, (size_t) r.n * n_luma * sizeof *lc, hipMemcpyHostToDevice, r.stream)); }
+  if (wantC) { HIPCHK(w.err_c.reserve(nce)); HIPCHK(w.cc.reserve((size_t) r.n * n_chroma)); HIPCHK(hipMemcpyAsync(w.cc.p, cc, (size_t) r.n * n_chroma * sizeof *cc, hipMemcpyHostToDevice, r.stream)); }
+  if (ncl || wantC) {
+    VxAlfCandParams p; memset(&p, 0, sizeof p);
+    p.luma = r.luma; p.chroma = r.chroma; p.luma_cands = w.lc.p; p.chroma_cands = w.cc.p; p.luma_err = w.err_l.p; p.chroma_err = w.err_c.p;
+    p.nctu = r.nctu; p.nb = r.nb; p.fixed_sets = fixed_sets; p.n_luma = n_luma; p.n_chroma = wantC ? n_chroma : 0;
+    const dim3 grid((unsigned) r.nctu, wantC ? 3u : 1u, (unsigned) r.n);      // one workgroup owns one (CTU, component, frame)
+    if (r.ev0) HIPCHK(hipEventRecord(r.ev0, r.stream));
+    hipLaunchKernelGGL(vvcx_alf_cand_kernel, grid, dim3(256), 0, r.stream, p);
+    HIPCHK(hipGetLastError());
+    if (r.ev0) HIPCHK(hipEventRecord(r.ev1, r.stream));
+    if (ncl) HIPCHK(hipMemcpyAsync(luma_err, w.err_l.p, nle * sizeof(long long), hipMemcpyDeviceToHost, r.stream));
+    if (wantC) HIPCHK(hipMemcpyAsync(chroma_err, w.err_c.p, nce * sizeof(long long), hipMemcpyDeviceToHost, r.stream));
+    HIPCHK(hipStreamSynchronize(r.stream));
+    if (r.ev0) HIPCHK(hipEventElapsedTime(&r.cand_ms, r.ev0, r.ev1));
+  }
+  if (n_chroma && !wantC) memset(chroma_err, 0, nce * sizeof(int64_t));      // no chroma statistics
+  return VVCX_OK;
+}
+
+// (E, y, pixAcc) of one block of nb-bin statistics with tap k read at clipping index clip[k]
+static void alf_gather(const int64_t *blk, int nb, int nc, const int *clip, AlfCov &s)
+{
+  const int64_t *ys = blk + (size_t) nb * nb * nc * nc;
+  s.clear();
+  for (int k = 0; k < nc - 1; k++) {
+    for (int l = 0; l < nc - 1; l++) s.E[k][l] = (double) blk[((size_t) (clip[k] * nb + clip[l]) * nc + k) * nc + l];
+    s.y[k] = (double) ys[clip[k] * nc + k];
+  }
+  s.pix = (double) ys[(size_t) nb * nc];
+}
+// tap k reads the same numbers at index a as at index b while the other taps stay at clip[]
+static bool alf_same_rows(const int64_t *blk, int nb, int nc, const int *clip, int k, int a, int b)
+{
+  const int64_t *ys = blk + (size_t) nb * nb * nc * nc;
+  if (ys[a * nc + k] != ys[b * nc + k] || blk[((size_t) (a * nb + a) * nc + k) * nc + k] != blk[((size_t) (b * nb + b) * nc + k) * nc + k]) return false;
+  for (int l = 0; l < nc - 1; l++) if (l != k && blk[((size_t) (a * nb + clip[l]) * nc + k) * nc + l] != blk[((size_t) (b * nb + clip[l]) * nc + k) * nc + l]) return false;
+  return true;
+}
+// The clipping indices of one filter on one block of 4-bin statistics (≙ AlfCovariance::optimizeFilter, EL 88-223, in this project's form): from index 0 everywhere the
+// best single move of one tap by +- step (2, then 1), judged by the least-squares error of the re-solved gathered system, while one improves; integer coefficients by
+// alf_quant on the gathered system; kept only if they predict less than the linear filter q_lin; then every index is lowered whose lower neighbour reads the same rows
+// or whose coefficient is 0 (≙ reduceClipCost, EL 68-86).  false: the linear filter stays (q, clip untouched)
+static bool alf_clip_search(const int64_t *blk, int nb, int nc, const int *q_lin, int *q, int *clip)
+{
+  const int n = nc - 1;
+  int c[12] = { 0 }, qn[12];
+  AlfCov s; alf_gather(blk, nb, nc, c, s);
+  const double e_lin = s.err_q(q_lin, n);
+  double best = alf_ls_error(s, n);
+  for (int step = 2; step >= 1; step--) for (;;) {
+    int bk = -1, bv = 0; double be = best;
+    for (int k = 0; k < n; k++) for (int d = -step; d <= step; d += 2 * step) {
+      const int v = c[k] + d, old = c[k];
+      if (v < 0 || v >= nb) continue;
+      c[k] = v; alf_gather(blk, nb, nc, c, s); c[k] = old;
+      const double e = alf_ls_error(s, n);
+      if (e < be) { be = e; bk = k; bv = v; }
+    }
+    if (bk < 0) break;
+    c[bk] = bv; best = be;
+  }
+  alf_gather(blk, nb, nc, c, s);
+  if (!(alf_quant(s, n, qn) < e_lin)) return false;
+  bool any = false;
+  for (int k = 0; k < n; k++) {
+    if (qn[k] == 0) c[k] = 0;
+    while (c[k] > 0 && alf_same_rows(blk, nb, nc, c, k, c[k], c[k] - 1)) c[k]--;
+    any |= c[k] != 0;
+  }
+  if (!any) return false;
+  for (int k = 0; k < n; k++) { q[k] = qn[k]; clip[k] = c[k]; }
+  return true;
+}
+
+struct AlfLumaSet { AlfLuma f; int clip[25][12]; bool valid, nonlinear; };
+static void alf_expand(const AlfLumaSet &t, vvcx_alf_luma_cand &cd)
+{
+  memset(&cd, 0, sizeof cd);
+  if (t.valid) for (int c = 0; c < 25; c++) for (int k = 0; k < 12; k++) { cd.coeff[c][k] = (int16_t) t.f.q[t.f.map[c]][k]; cd.clip_idx[c][k] = (uint8_t) t.clip[t.f.map[c]][k]; }
+}
+// filters from the frame sums `sums` ([25][szl]); with `nonlinear` the clip search per group on the summed 4-bin blocks (the merge itself reads bin 0)
+static void alf_luma_sets(const int64_t *sums, int nb, double lambda, int max_filters, bool nonlinear, AlfLumaSet &lin, AlfLumaSet &nl)
+{
+  const size_t szl = alf_stat_size(nb, 13);
+  AlfCov cls[25];
+  for (int c = 0; c < 25; c++) { cls[c].clear(); cls[c].add(sums + (size_t) c * szl, nb, 13); }
+  alf_derive_luma(cls, lambda, max_filters, lin.f);
+  memset(lin.clip, 0, sizeof lin.clip); lin.valid = true; lin.nonlinear = false;
+  nl.valid = false;
+  if (!nonlinear) return;
+  nl = lin;
+  std::vector<int64_t> blk(szl);
+  for (int g = 0; g < lin.f.n; g++) {
+    std::fill(blk.begin(), blk.end(), 0);
+    for (int c = 0; c < 25; c++) if (lin.f.map[c] == g) for (size_t i = 0; i < szl; i++) blk[i] += sums[(size_t) c * szl + i];
+    if (alf_clip_search(blk.data(), nb, 13, lin.f.q[g], nl.f.q[g], nl.clip[g])) {
+      nl.nonlinear = true;
+      nl.f.bits += alf_coeff_bits(nl.f.q[g], 12) - alf_coeff_bits(lin.f.q[g], 12);
+    }
+  }
+  nl.f.bits += 2 * 12 * nl.f.n;      // two bits per clipping index of every filter once the flag is on
+  nl.valid = nl.nonlinear;
+}
+
+static int alf_decide_frames(AlfRes &r, bool chroma, const double lambda[3], int max_luma_filters, int flags, vvcx_alf_aps *aps, vvcx_alf_slice *slices, vvcx_alf_ctu *ctus)
+{
+  const int n = r.n, nctu = r.nctu, nb = r.nb;
+  const bool nlL = (flags & VVCX_ALF_NONLINEAR_LUMA) != 0, nlC = (flags & VVCX_ALF_NONLINEAR_CHROMA) != 0 && chroma, fx = (flags & VVCX_ALF_FIXED_SETS) != 0;
+  const size_t szl = alf_stat_size(nb, 13), szc = alf_stat_size(nb, 7);
+  const double lamC = .5 * (lambda[1] + lambda[2]);
+  std::vector<int64_t> sl((size_t) n * 25 * szl), sc(chroma ? (size_t) n * 2 * szc : 0), slB;
+  // ---- round 0: filters from all CTUs, the CTUs' choices against them (and against the fixed sets)
+  if (const int rc = alf_sums(r, nullptr, sl.data(), chroma ? sc.data() : nullptr)) return rc;
+  std::vector<AlfLumaSet> set((size_t) n * 4);      // per frame: linear / nonlinear from the flags-0 mask, linear / nonlinear from the CTUs that chose the new set over the fixed ones
+  std::vector<vvcx_alf_luma_cand> lc((size_t) n * 4);
+  std::vector<vvcx_alf_chroma_cand> cc((size_t) n * 2);
+  std::vector<int> qc((size_t) n * 6), qcn((size_t) n * 6), clipc((size_t) n * 6); std::vector<uint8_t> cnl((size_t) n, 0);
+  AlfLumaSet none; none.valid = false;
+  for (int f = 0; f < n; f++) {
+    alf_luma_sets(sl.data() + (size_t) f * 25 * szl, nb, lambda[0], max_luma_filters, false, set[(size_t) f * 4], none);
+    alf_expand(set[(size_t) f * 4], lc[(size_t) f]);
+    if (chroma) {
+      AlfCov s; s.clear(); s.add(sc.data() + (size_t) f * 2 * szc, nb, 7); s.add(sc.data() + ((size_t) f * 2 + 1) * szc, nb, 7);
+      alf_quant(s, 6, &qc[(size_t) f * 6]);
+      memset(&cc[(size_t) f], 0, sizeof cc[0]);
+      for (int k = 0; k < 6; k++) cc[(size_t) f].coeff[k] = (int16_t) qc[(size_t) f * 6 + k];
+    }
+  }
+  const int n0 = 16 * (int) fx + 1;
+  std::vector<int64_t> e0((size_t) n * nctu * n0), ec0(chroma ? (size_t) n * nctu * 2 : 0);
+  if (const int rc = alf_errors(r, fx, lc.data(), 1, chroma ? cc.data() : nullptr, chroma ? 1 : 0, e0.data(), ec0.data())) return rc;
+  std::vector<uint8_t> maskA((size_t) n * nctu * 3, 0), maskB;
+  std::vector<int> onA((size_t) n, 0), onB((size_t) n, 0), onC((size_t) n, 0);
+  for (int f = 0; f < n; f++) for (int a = 0; a < nctu; a++) {
+    const size_t i = (size_t) f * nctu + a;
+    maskA[i * 3] = (double) e0[i * n0 + n0 - 1] / 16384. + lambda[0] * 1. < 0.;      // an enabled CTU codes one more bin (alf_use_aps_flag)
+    onA[(size_t) f] += maskA[i * 3];
+    if (chroma) for (int c = 0; c < 2; c++) { maskA[i * 3 + 1 + c] = ec0[i * 2 + c] < 0; onC[(size_t) f] += maskA[i * 3 + 1 + c]; }
+  }
+  bool needB = false;
+  if (fx) {
+    maskB = maskA;
+    for (int f = 0; f < n; f++) for (int a = 0; a < nctu; a++) {
+      const size_t i = (size_t) f * nctu + a;
+      double best = 0.; int ch = -1;
+      for (int s = 0; s < 16; s++) { const double v = (double) e0[i * n0 + s] / 16384. + 5. * lambda[0]; if (v < best) { best = v; ch = s; } }
+      { const double v = (double) e0[i * n0 + 16] / 16384. + lambda[0]; if (v < best) { best = v; ch = 16; } }
+      maskB[i * 3] = ch == 16; onB[(size_t) f] += ch == 16;
+      needB |= maskB[i * 3] != maskA[i * 3];
+    }
+  }
+  // ---- round 1: the filters once more from the CTUs that use them, the clip search on those sums, the last evaluation
+  if (const int rc = alf_sums(r, maskA.data(), sl.data(), chroma ? sc.data() : nullptr)) return rc;
+  if (needB) { slB.resize(sl.size()); if (const int rc = alf_sums(r, maskB.data(), slB.data(), nullptr)) return rc; }
+  const int n1 = 1 + (int) nlL + (fx ? 1 + (int) nlL : 0), nc1 = 1 + (int) nlC, iB = 1 + (int) nlL;
+  std::vector<vvcx_alf_luma_cand> lc1((size_t) n * n1);
+  for (int f = 0; f < n; f++) {
+    AlfLumaSet *t = &set[(size_t) f * 4];
+    if (onA[(size_t) f]) alf_luma_sets(sl.data() + (size_t) f * 25 * szl, nb, lambda[0], max_luma_filters, nlL, t[0], t[1]); else t[1].valid = false;
+    t[2].valid = t[3].valid = false;
+    if (fx && onB[(size_t) f]) {
+      if (needB) alf_luma_sets(slB.data() + (size_t) f * 25 * szl, nb, lambda[0], max_luma_filters, nlL, t[2], t[3]);
+      else { t[2] = t[0]; t[3] = t[1]; t[2].valid = t[0].valid && onA[(size_t) f]; }
+    }
+    alf_expand(t[0], lc1[(size_t) f * n1]);
+    if (nlL) alf_expand(t[1], lc1[(size_t) f * n1 + 1]);
+    if (fx) { alf_expand(t[2], lc1[(size_t) f * n1 + iB]); if (nlL) alf_expand(t[3], lc1[(size_t) f * n1 + iB + 1]); }
+    if (chroma) {
+      int *q = &qc[(size_t) f * 6];
+      std::vector<int64_t> blk(szc);
+      for (size_t i = 0; i < szc; i++) blk[i] = sc[(size_t) f * 2 * szc + i] + sc[((size_t) f * 2 + 1) * szc + i];
+      if (onC[(size_t) f]) { AlfCov s; s.clear(); s.add(blk.data(), nb, 7); alf_quant(s, 6, q); }
+      if (nlC && onC[(size_t) f]) cnl[(size_t) f] = alf_clip_search(blk.data(), nb, 7, q, &qcn[(size_t) f * 6], &clipc[(size_t) f * 6]);
+      memset(&cc[(size_t) f * nc1], 0, sizeof cc[0] * (size_t) nc1);
+      for (int k = 0; k < 6; k++) {
+        cc[(size_t) f * nc1].coeff[k] = (int16_t) q[k];
+        if (cnl[(size_t) f]) { cc[(size_t) f * nc1 + 1].coeff[k] = (int16_t) qcn[(size_t) f * 6 + k]; cc[(size_t) f * nc1 + 1].clip_idx[k] = (uint8_t) clipc[(size_t) f * 6 + k]; }
+      }
+    }
+  }
+  std::vector<int64_t> e1((size_t) n * nctu * n1), ec1(chroma ? (size_t) n * nctu * 2 * nc1 : 0);
+  if (const int rc = alf_errors(r, 0, lc1.data(), n1, chroma ? cc.data() : nullptr, chroma ? nc1 : 0, e1.data(), ec1.data())) return rc;
+  // ---- per frame the least of the complete decisions: J = sum over CTUs (predicted error + lambda * bits) + lambda * parameter-set bits, relative to everything off
+  for (int f = 0; f < n; f++) {
+    vvcx_alf_aps &ap = aps[f]; vvcx_alf_slice &sl_o = slices[f]; vvcx_alf_ctu *cu = ctus + (size_t) f * nctu;
+    const AlfLumaSet *t = &set[(size_t) f * 4];
+    memset(&ap, 0, sizeof ap); memset(&sl_o, 0, sizeof sl_o); memset(cu, 0, sizeof *cu * (size_t) nctu);
+    sl_o.n_luma_aps = 1; sl_o.luma_aps[0] = 0; sl_o.chroma_aps = -1;
+    ap.num_luma_filters = 1;
+    for (int a = 0; a < nctu; a++) cu[a].set = 16;
+    const int64_t *ef = e0.data() + (size_t) f * nctu * n0, *en = e1.data() + (size_t) f * nctu * n1;
+    // the flags-0 decision: vvcx_alf_decide's
+    std::vector<int> choice((size_t) nctu, -1), trial((size_t) nctu);      // per CTU: -1 off, 0..15 fixed set, 16 the new set
+    double bestJ = 0.; int bestSet = -1;
+    if (onA[(size_t) f]) {
+      double gain = 0;
+      for (int a = 0; a < nctu; a++) if (maskA[((size_t) f * nctu + a) * 3]) gain += -(double) en[(size_t) a * n1] / 16384. - lambda[0];
+      if (gain > lambda[0] * t[0].f.bits) {
+        bestJ = lambda[0] * t[0].f.bits - gain; bestSet = 0;
+        for (int a = 0; a < nctu; a++) choice[(size_t) a] = maskA[((size_t) f * nctu + a) * 3] ? 16 : -1;
+      }
+    }
+    // the decisions the flags add: per CTU the least of off, the fixed sets and the new set x (x < 0: no new set)
+    for (int x = fx ? -1 : 1; x < (fx || nlL ? 4 : 0); x++) {
+      if (x >= 0 && (!t[x].valid || (!fx && x != 1))) continue;
+      const int col = x < 0 ? 0 : x < 2 ? x : iB + (x - 2);
+      double J = 0; int used = 0;
+      for (int a = 0; a < nctu; a++) {
+        double b = 0.; int ch = -1;
+        if (fx) for (int s = 0; s < 16; s++) { const double v = (double) ef[(size_t) a * n0 + s] / 16384. + 5. * lambda[0]; if (v < b) { b = v; ch = s; } }
+        if (x >= 0) { const double v = (double) en[(size_t) a * n1 + col] / 16384. + lambda[0]; if (v < b) { b = v; ch = 16; } }
+        trial[(size_t) a] = ch; J += b; used += ch == 16;
+      }
+      if (x >= 0) { if (!used) continue; J += lambda[0] * t[x].f.bits; }
+      if (J < bestJ) { bestJ = J; bestSet = x >= 0 ? x : -1; choice = trial; }
+    }
+    bool newUsed = false;
+    for (int a = 0; a < nctu; a++) {
+      const int ch = choice[(size_t) a];
+      cu[a].flag[0] = ch >= 0; if (ch >= 0) cu[a].set = (int8_t) ch;
+      newUsed |= ch == 16;
+    }
+    if (newUsed) {
+      const AlfLumaSet &b = t[bestSet];
+      ap.num_luma_filters = b.f.n; ap.nonlinear_luma = b.nonlinear;
+      for (int c = 0; c < 25; c++) ap.class_to_filter[c] = b.f.map[c];
+      for (int g = 0; g < b.f.n; g++) for (int k = 0; k < 12; k++) { ap.luma_coeff[g][k] = (int16_t) b.f.q[g][k]; ap.luma_clip_idx[g][k] = (uint8_t) b.clip[g][k]; }
+    } else if (fx && bestJ < 0.) sl_o.n_luma_aps = 0;      // fixed sets only: the slice carries no luma parameter set
+    // chroma: one alternative for both components, flags per component; the nonlinear one where it is cheaper
+    if (chroma && onC[(size_t) f]) {
+      const int64_t *ec = ec1.data() + (size_t) f * nctu * 2 * nc1;
+      const int *q = &qc[(size_t) f * 6], *qn = &qcn[(size_t) f * 6];
+      double gain = 0, J = 0., Jn = 0.;
+      for (int i = 0; i < 2 * nctu; i++) if (maskA[((size_t) f * nctu + (i >> 1)) * 3 + 1 + (i & 1)]) gain += -(double) ec[(size_t) i * nc1] / 16384.;
+      const int bits = 1 + alf_ue_bits(0) + alf_coeff_bits(q, 6);
+      const bool lin = gain > lamC * bits;      // the parameter set's bits weigh with the mean of the two chroma lambdas
+      if (lin) J = lamC * bits - gain;
+      bool useN = false;
+      if (cnl[(size_t) f]) {
+        for (int i = 0; i < 2 * nctu; i++) Jn += std::min(0., (double) ec[(size_t) i * nc1 + 1] / 16384.);
+        Jn += lamC * (1 + alf_ue_bits(0) + alf_coeff_bits(qn, 6) + 2 * 6);
+        useN = Jn < J;
+      }
+      if (lin || useN) {
+        sl_o.chroma_aps = 0; ap.num_chroma_alt = 1; ap.nonlinear_chroma[0] = useN;
+        for (int k = 0; k < 6; k++) { ap.chroma_coeff[0][k] = (int16_t) (useN ? qn[k] : q[k]); ap.chroma_clip_idx[0][k] = (uint8_t) (useN ? clipc[(size_t) f * 6 + k] : 0); }
+        for (int i = 0; i < 2 * nctu; i++) cu[i >> 1].flag[1 + (i & 1)] = useN ? ec[(size_t) i * nc1 + 1] < 0 : maskA[((size_t) f * nctu + (i >> 1)) * 3 + 1 + (i & 1)];
+      }
+    }
+  }
+  return VVCX_OK;
+}
+static int alf_decide_args(const double lambda[3], int max_luma_filters, int flags, int nb)
+{
+  if (!lambda || max_luma_filters < 1 || max_luma_filters > 25 || !(lambda[0] >= 0) || !(lambda[1] >= 0) || !(lambda[2] >= 0) || flags < 0 || flags > 7)
+    return fail(VVCX_ERR_ARG, "ALF decision: filter count / lambdas / flags");
+  if ((flags & (VVCX_ALF_NONLINEAR_LUMA | VVCX_ALF_NONLINEAR_CHROMA)) && nb != 4) return fail(VVCX_ERR_ARG, "ALF decision: nonlinear filters need statistics with 4 clipping bins");
+  return VVCX_OK;
+}
+static int alf_resident(vvcx_handle *h, void *hip_stream, AlfRes &r)
+{
+  if (!h->alf_res_valid) return fail(VVCX_ERR_STATE, "no resident ALF statistics (vvcx_alf_statistics_resident), or a call has touched the bound pictures since");
+  r.luma = h->alf_stat_luma_d.p; r.chroma = h->alf_res_chroma ? h->alf_stat_chroma_d.p : nullptr; r.n = h->alf_res_n; r.nctu = h->ctus_w * h->ctus_h; r.nb = h->alf_res_bins;
+  r.w = &h->alf_work; r.stream = (hipStream_t) hip_stream; r.ev0 = h->ev0; r.ev1 = h->ev1; r.sum_ms = h->last_alf_sum_ms; r.cand_ms = h->last_alf_cand_ms;
+  return VVCX_OK;
+}
+}      // namespace
+
+extern "C" int vvcx_alf_frame_statistics(vvcx_handle *h, const uint8_t *ctu_on, int64_t *luma, int64_t *chroma, void *hip_stream)
+{
+  NOT_PENDING(h);
+  if (!h || !luma) return fail(VVCX_ERR_ARG, "null argument");
+  AlfRes r;
+  if (const int rc = alf_resident(h, hip_stream, r)) return rc;
+  ON_DEVICE(h->cfg.device);
+  const int rc = alf_sums(r, ctu_on, luma, chroma);
+  h->last_alf_sum_ms = r.sum_ms;
+  return rc;
+}
+extern "C" int vvcx_alf_candidate_errors(vvcx_handle *h, int fixed_sets, const vvcx_alf_luma_cand *luma_cands, int n_luma, const vvcx_alf_chroma_cand *chroma_cands, int n_chroma,
+                                         int64_t *luma_err, int64_t *chroma_err, void *hip_stream)
+{
+  NOT_PENDING(h);
+  if (!h) return fail(VVCX_ERR_ARG, "null handle");
+  AlfRes r;
+  if (const int rc = alf_resident(h, hip_stream, r)) return rc;
+  ON_DEVICE(h->cfg.device);
+  const int rc = alf_errors(r, fixed_sets, luma_cands, n_luma, chroma_cands, n_chroma, luma_err, chroma_err);
+  h->last_alf_cand_ms = r.cand_ms;
+  return rc;
+}
+extern "C" int vvcx_alf_decide_resident(vvcx_handle *h, const double lambda[3], int max_luma_filters, int flags, vvcx_alf_aps *aps, vvcx_alf_slice *slices, vvcx_alf_ctu *ctus,
+                                        void *hip_stream)
+{
+  NOT_PENDING(h);
+  if (!h || !aps || !slices || !ctus) return fail(VVCX_ERR_ARG, "null argument");
+  AlfRes r;
+  if (const int rc = alf_resident(h, hip_stream, r)) return rc;
+  if (const int rc = alf_decide_args(lambda, max_luma_filters, flags, r.nb)) return rc;
+  ON_DEVICE(h->cfg.device);
+  const int rc = alf_decide_frames(r, r.chroma != nullptr, lambda, max_luma_filters, flags, aps, slices, ctus);
+  h->last_alf_sum_ms = r.sum_ms; h->last_alf_cand_ms = r.cand_ms;
+  return rc;
+}
+extern "C" float vvcx_last_alf_sum_ms(const vvcx_handle *h) { return h ? h->last_alf_sum_ms : 0.f; }
+extern "C" float vvcx_last_alf_cand_ms(const vvcx_handle *h) { return h ? h->last_alf_cand_ms : 0.f; }
+
+extern "C" int vvcx_alf_evaluate_picture(int pic_w, int pic_h, int bit_depth, int n_bins, const uint16_t *const org[3], const uint16_t *const rec[3], const uint8_t *ctu_on,
+                                         int fixed_sets, const vvcx_alf_luma_cand *luma_cands, int n_luma, const vvcx_alf_chroma_cand *chroma_cands, int n_chroma,
+                                         int64_t *luma_sum, int64_t *chroma_sum, int64_t *luma_err, int64_t *chroma_err, int device)
+{
+  if (const int rc = alf_picture_args("vvcx_alf_evaluate_picture", pic_w, pic_h, bit_depth, n_bins, org, rec)) return rc;
+  const bool sums = luma_sum != nullptr, errs = luma_err || chroma_err;
+  if (!sums && !errs) return fail(VVCX_ERR_ARG, "vvcx_alf_evaluate_picture: no output asked for");
+  ON_DEVICE(device);
+  DevBuf<long long> luma_d, chroma_d; AlfWork work;
+  if (const int rc = alf_stats_of_planes(pic_w, pic_h, bit_depth, n_bins, org, rec, true, luma_d, chroma_d)) return rc;
+  AlfRes r; memset(&r, 0, sizeof r);
+  r.luma = luma_d.p; r.chroma = chroma_d.p; r.n = 1; r.nctu = ((pic_w + 127) / 128) * ((pic_h + 127) / 128); r.nb = n_bins; r.w = &work;
+  if (sums) if (const int rc = alf_sums(r, ctu_on, luma_sum, chroma_sum)) return rc;
+  if (errs) if (const int rc = alf_errors(r, fixed_sets, luma_cands, n_luma, chroma_cands, n_chroma, luma_err, chroma_err)) return rc;
+  return VVCX_OK;
+}
+extern "C" int vvcx_alf_decide_picture(int pic_w, int pic_h, int bit_depth, int n_bins, const uint16_t *const org[3], const uint16_t *const rec[3], const double lambda[3],
+                                       int max_luma_filters, int flags, vvcx_alf_aps *aps, vvcx_alf_slice *slice, vvcx_alf_ctu *ctus, int device)
+{
+  if (!aps || !slice || !ctus) return fail(VVCX_ERR_ARG, "null argument");
+  if (const int rc = alf_picture_args("vvcx_alf_decide_picture", pic_w, pic_h, bit_depth, n_bins, org, rec)) return rc;
+  if (const int rc = alf_decide_args(lambda, max_luma_filters, flags, n_bins)) return rc;
+  ON_DEVICE(device);
+  DevBuf<long long> luma_d, chroma_d; AlfWork work;
+  if (const int rc = alf_stats_of_planes(pic_w, pic_h, bit_depth, n_bins, org, rec, true, luma_d, chroma_d)) return rc;
+  AlfRes r; memset(&r, 0, sizeof r);
+  r.luma = luma_d.p; r.chroma = chroma_d.p; r.n = 1; r.nctu = ((pic_w + 127) / 128) * ((pic_h + 127) / 128); r.nb = n_bins; r.w = &work;
+  return alf_decide_frames(r, true, lambda, max_luma_filters, flags, aps, slice, ctus);
 }
 
 // the same two kernels on a picture the caller describes by a CU table (host memory in, host memory out): the unit maps the kernels read are built here from the rows

@@ -145,6 +145,27 @@ struct VxAlfStatParams {
   int32_t clip[2][4];             // clipping value of bin b: luma, chroma
 };
 
+// ALF encoder decision passes over the resident statistics (vvcx_alf_eval.hip).  The candidate records have the layout of vvcx_alf_luma_cand / vvcx_alf_chroma_cand
+#define VX_ALF_MAX_CAND 64        // candidates of one call per component, the 16 fixed sets included
+struct VxAlfLumaCand { int16_t coeff[25][12]; uint8_t clip_idx[25][12]; };
+struct VxAlfChromaCand { int16_t coeff[6]; uint8_t clip_idx[6]; };
+struct VxAlfSumParams {
+  const long long *luma, *chroma; // the statistics of n frames as VxAlfStatParams describes them (chroma NULL: the grid has no chroma row)
+  const uint8_t *ctu_on;          // [frame][ctu][3]; NULL: every CTU counts
+  long long *luma_out;            // [frame][25][size_l]
+  long long *chroma_out;          // [frame][2][size_c]
+  int32_t nctu, pad_;
+  uint64_t size_l, size_c;
+};
+struct VxAlfCandParams {
+  const long long *luma, *chroma;
+  const VxAlfLumaCand *luma_cands;       // [frame][n_luma]
+  const VxAlfChromaCand *chroma_cands;   // [frame][n_chroma]
+  long long *luma_err;            // [frame][ctu][16 * fixed_sets + n_luma]
+  long long *chroma_err;          // [frame][ctu][2][n_chroma]
+  int32_t nctu, nb, fixed_sets, n_luma, n_chroma, pad_;
+};
+
 // payload rewrite (vvcx_rewrite_kernel_*, vvcx_kernel.hip): every tile's slice_data once more from the stored CU maps and levels, with the SAO / ALF CTU syntax
 // (CABACWriter::coding_tree_unit, EL/CABACWriter.cpp:254-309) in front of each coding tree.  One workgroup per (frame, tile), thread 0 codes; no workgroup waits on another
 #define VXD_NUM_CS_CTX  15                              // the models of that syntax (vvcx_ctu_syntax_tables.h VX_CS_NUM_CTX), kept beside the VXD_NUM_CTX ones

@@ -243,6 +243,83 @@ def alf_decide(luma, chroma, width, height, bit_depth, lambdas, n_bins=1, max_lu
     return dict(aps=aps.to_row()[None, :], luma_aps=[int(sl.luma_aps[k]) for k in range(sl.n_luma_aps)], chroma_aps=int(sl.chroma_aps), ctu=ctu.astype(np.int32))
 
 
+ALF_NONLINEAR_LUMA = 1       # flags of alf_decide_picture / VvcxEncoder.alf_decide_resident
+ALF_NONLINEAR_CHROMA = 2
+ALF_FIXED_SETS = 4
+ALF_LUMA_CAND = np.dtype([("coeff", "<i2", (25, 12)), ("clip_idx", "u1", (25, 12))])      # vvcx_alf_luma_cand: per class, class_to_filter applied
+ALF_CHROMA_CAND = np.dtype([("coeff", "<i2", (6,)), ("clip_idx", "u1", (6,))])            # vvcx_alf_chroma_cand
+
+
+def alf_luma_cand(aps_row):
+    """the luma filters of one parameter set (a row of synth.alf_test_params' form) as one candidate record: the filter of every class, its clipping indices when the
+    set is nonlinear"""
+    cd = np.zeros((), ALF_LUMA_CAND)
+    for c in range(25):
+        g = int(aps_row[1 + c])
+        cd["coeff"][c] = aps_row[27 + 12 * g:39 + 12 * g]
+        if aps_row[26]:
+            cd["clip_idx"][c] = aps_row[327 + 12 * g:339 + 12 * g]
+    return cd
+
+
+def alf_chroma_cand(aps_row, alt=0):
+    cd = np.zeros((), ALF_CHROMA_CAND)
+    cd["coeff"] = aps_row[636 + 6 * alt:642 + 6 * alt]
+    if aps_row[628 + alt]:
+        cd["clip_idx"] = aps_row[684 + 6 * alt:690 + 6 * alt]
+    return cd
+
+
+def _alf_cands(luma_cands, chroma_cands, n):
+    lc = np.ascontiguousarray(np.zeros((n, 0), ALF_LUMA_CAND) if luma_cands is None else luma_cands, ALF_LUMA_CAND).reshape(n, -1)
+    cc = np.ascontiguousarray(np.zeros((n, 0), ALF_CHROMA_CAND) if chroma_cands is None else chroma_cands, ALF_CHROMA_CAND).reshape(n, -1)
+    return lc, cc
+
+
+def _alf_decision(aps, sl, ctu, nctu):
+    """the per-frame dicts (synth.alf_test_params' form) of a decision's C arrays"""
+    ctu = ctu.reshape(-1, nctu, 6).astype(np.int32)
+    return [dict(aps=aps[i].to_row()[None, :], luma_aps=[int(sl[i].luma_aps[k]) for k in range(sl[i].n_luma_aps)], chroma_aps=int(sl[i].chroma_aps), ctu=ctu[i]) for i in range(len(ctu))]
+
+
+def alf_evaluate_picture(org, rec, bit_depth, n_bins=1, ctu_on=None, fixed_sets=False, luma_cands=None, chroma_cands=None, want_sums=True, device=0, lib_path=None):
+    """vvcx_alf_evaluate_picture: the two device passes of the ALF decision on one picture in host memory -> (luma sums int64 [25, .], chroma sums [2, .], luma errors
+    int64 [ctus, 16 * fixed_sets + candidates], chroma errors [ctus, 2, candidates]); ctu_on uint8 [ctus, 3] (None: all); candidates as ALF_LUMA_CAND / ALF_CHROMA_CAND
+    arrays; the pair that was not asked for is None"""
+    L = load_library(lib_path)
+    o = [np.ascontiguousarray(p.astype(np.uint16)) for p in org]; r = [np.ascontiguousarray(p.astype(np.uint16)) for p in rec]
+    h, w = r[0].shape
+    nctu = ((w + 127) // 128) * ((h + 127) // 128)
+    szl, szc = alf_stat_sizes(n_bins if n_bins in (1, 4) else 1)
+    lc, cc = _alf_cands(luma_cands, chroma_cands, 1)
+    ncl = 16 * int(bool(fixed_sets)) + lc.shape[1]
+    want_err = ncl > 0 or cc.shape[1] > 0
+    sl = np.zeros((25, szl), np.int64); sc = np.zeros((2, szc), np.int64)
+    el = np.zeros((nctu, ncl), np.int64); ec = np.zeros((nctu, 2, cc.shape[1]), np.int64)
+    on = None if ctu_on is None else np.ascontiguousarray(ctu_on, np.uint8).reshape(nctu, 3)
+    op = (C.c_void_p * 3)(*[p.ctypes.data for p in o]); rp = (C.c_void_p * 3)(*[p.ctypes.data for p in r])
+    L.vvcx_alf_evaluate_picture.argtypes = [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int]
+    _chk(L, L.vvcx_alf_evaluate_picture(w, h, bit_depth, n_bins, op, rp, None if on is None else on.ctypes.data, int(bool(fixed_sets)), lc.ctypes.data, lc.shape[1],
+                                        cc.ctypes.data, cc.shape[1], sl.ctypes.data if want_sums else None, sc.ctypes.data if want_sums else None,
+                                        el.ctypes.data if want_err else None, ec.ctypes.data if want_err else None, device))
+    return (sl if want_sums else None, sc if want_sums else None, el if want_err else None, ec if want_err else None)
+
+
+def alf_decide_picture(org, rec, bit_depth, lambdas, n_bins=1, max_luma_filters=25, flags=0, device=0, lib_path=None):
+    """vvcx_alf_decide_picture: statistics, frame sums, candidate errors and the decision (flags: ALF_NONLINEAR_LUMA | ALF_NONLINEAR_CHROMA | ALF_FIXED_SETS) of one
+    picture in host memory -> a dict of the form alf_decide returns (luma_aps is [] when the slice carries no luma set)"""
+    L = load_library(lib_path)
+    o = [np.ascontiguousarray(p.astype(np.uint16)) for p in org]; r = [np.ascontiguousarray(p.astype(np.uint16)) for p in rec]
+    h, w = r[0].shape
+    nctu = ((w + 127) // 128) * ((h + 127) // 128)
+    lam = np.ascontiguousarray(lambdas, np.float64)
+    aps = (AlfAps * 1)(); sl = (AlfSlice * 1)(); ctu = np.zeros((nctu, 6), np.int8)
+    op = (C.c_void_p * 3)(*[p.ctypes.data for p in o]); rp = (C.c_void_p * 3)(*[p.ctypes.data for p in r])
+    L.vvcx_alf_decide_picture.argtypes = [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int]
+    _chk(L, L.vvcx_alf_decide_picture(w, h, bit_depth, n_bins, op, rp, lam.ctypes.data, int(max_luma_filters), int(flags), C.addressof(aps), C.addressof(sl), ctu.ctypes.data, device))
+    return _alf_decision(aps, sl, ctu, nctu)[0]
+
+
 def lmcs_analyze_device(ptrs, strides, width, height, bit_depth, qp, update_ctrl=1, lib_path=None):
     """vvcx_lmcs_analyze_device: the same analysis on planes that are in device memory (ptrs: three device addresses, strides in samples)"""
     L = load_library(lib_path)
@@ -371,6 +448,57 @@ class VvcxEncoder:
         self.L.vvcx_last_alf_stats_ms.argtypes = [C.c_void_p]
         self._chk(self.L.vvcx_alf_statistics_bound_frames(self.h, int(frame_first), int(n), int(n_bins), luma.ctypes.data, None if chroma is None else chroma.ctypes.data, None))
         return luma, chroma, float(self.L.vvcx_last_alf_stats_ms(self.h))
+
+    def alf_statistics_resident(self, frame_first=0, n=None, n_bins=1):
+        """vvcx_alf_statistics_resident: the same statistics, kept in device memory for alf_frame_statistics / alf_candidate_errors / alf_decide_resident; returns the
+        kernel time in ms"""
+        n = self.n_frames - frame_first if n is None else n
+        self.L.vvcx_alf_statistics_resident.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        self.L.vvcx_last_alf_stats_ms.restype = C.c_float
+        self.L.vvcx_last_alf_stats_ms.argtypes = [C.c_void_p]
+        self._alf_res = None
+        self._chk(self.L.vvcx_alf_statistics_resident(self.h, int(frame_first), int(n), int(n_bins), None))
+        self._alf_res = (int(n), int(n_bins))
+        return float(self.L.vvcx_last_alf_stats_ms(self.h))
+
+    def _alf_resident_shape(self):
+        n, nb = getattr(self, "_alf_res", None) or (1, 1)      # nothing resident: the library refuses the call
+        return (n, nb) + alf_stat_sizes(nb)
+
+    def alf_pass_ms(self):
+        """(vvcx_last_alf_sum_ms, vvcx_last_alf_cand_ms): HIP-event time of the last frame-sum and candidate-error kernels of this handle"""
+        for f in (self.L.vvcx_last_alf_sum_ms, self.L.vvcx_last_alf_cand_ms):
+            f.restype = C.c_float; f.argtypes = [C.c_void_p]
+        return float(self.L.vvcx_last_alf_sum_ms(self.h)), float(self.L.vvcx_last_alf_cand_ms(self.h))
+
+    def alf_frame_statistics(self, ctu_on=None):
+        """vvcx_alf_frame_statistics: the resident statistics summed over the CTUs whose byte of ctu_on uint8 [n, ctus, 3] is set (None: all) -> (luma int64 [n, 25, .],
+        chroma int64 [n, 2, .])"""
+        n, nb, szl, szc = self._alf_resident_shape()
+        luma = np.zeros((n, 25, szl), np.int64); chroma = np.zeros((n, 2, szc), np.int64)
+        on = None if ctu_on is None else np.ascontiguousarray(ctu_on, np.uint8).reshape(n, self.ctus_per_frame, 3)
+        self.L.vvcx_alf_frame_statistics.argtypes = [C.c_void_p] * 5
+        self._chk(self.L.vvcx_alf_frame_statistics(self.h, None if on is None else on.ctypes.data, luma.ctypes.data, chroma.ctypes.data, None))
+        return luma, chroma
+
+    def alf_candidate_errors(self, fixed_sets=False, luma_cands=None, chroma_cands=None):
+        """vvcx_alf_candidate_errors: candidates per resident frame (ALF_LUMA_CAND [n, k], ALF_CHROMA_CAND [n, m]) -> (int64 [n, ctus, 16 * fixed_sets + k],
+        int64 [n, ctus, 2, m])"""
+        n, nb, _, _ = self._alf_resident_shape()
+        lc, cc = _alf_cands(luma_cands, chroma_cands, n)
+        el = np.zeros((n, self.ctus_per_frame, 16 * int(bool(fixed_sets)) + lc.shape[1]), np.int64); ec = np.zeros((n, self.ctus_per_frame, 2, cc.shape[1]), np.int64)
+        self.L.vvcx_alf_candidate_errors.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self.L.vvcx_alf_candidate_errors(self.h, int(bool(fixed_sets)), lc.ctypes.data, lc.shape[1], cc.ctypes.data, cc.shape[1], el.ctypes.data, ec.ctypes.data, None))
+        return el, ec
+
+    def alf_decide_resident(self, lambdas, max_luma_filters=25, flags=0):
+        """vvcx_alf_decide_resident: the decision of every resident frame -> one dict of alf_decide's form per frame (each with its own parameter set as aps[0])"""
+        n, _, _, _ = self._alf_resident_shape()
+        lam = np.ascontiguousarray(lambdas, np.float64)
+        aps = (AlfAps * n)(); sl = (AlfSlice * n)(); ctu = np.zeros((n, self.ctus_per_frame, 6), np.int8)
+        self.L.vvcx_alf_decide_resident.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self.L.vvcx_alf_decide_resident(self.h, lam.ctypes.data, int(max_luma_filters), int(flags), C.addressof(aps), C.addressof(sl), ctu.ctypes.data, None))
+        return _alf_decision(aps, sl, ctu, self.ctus_per_frame)
 
     def get_levels(self, frame):
         """quantised levels of the coded picture: three int16 planes (Y, Cb, Cr)"""
