@@ -229,7 +229,9 @@ struct VxRbItem { double cost; uint64_t dist, bits; int32_t cbf, sum0, test, wav
 #define VXD_OFF_ISP_BEST (VXD_OFF_ISP + VXD_NW * VXD_ISP_WAVE * 2)
 #define VXD_OFF_JCCR    ((VXD_OFF_ISP_BEST + 2 * 4096 * 2 + 255) & ~255)
 #define VXD_JCCR_WAVE   (6 * 1024 * 2)
-#define VXD_OFF_CACHE   ((VXD_OFF_JCCR + VXD_NW * VXD_JCCR_WAVE + 255) & ~255)
+// chroma full-RD: per wave two snapshots of its working models, behind the separately coded pair and behind the best joint candidate (chroma_rd_rounds)
+#define VXD_OFF_JCTX    ((VXD_OFF_JCCR + VXD_NW * VXD_JCCR_WAVE + 255) & ~255)
+#define VXD_OFF_CACHE   ((VXD_OFF_JCTX + VXD_NW * 2 * VXD_CTXSNAP + 255) & ~255)
 #define VXD_OFF_CACHE_LEV (VXD_OFF_CACHE + VXD_CACHE_ENTRIES * (int) sizeof(VxCacheEnt))
 #define VXD_OFF_META    (VXD_OFF_CACHE_LEV + VXD_CACHE_DIM * VXD_CACHE_DIM * 2)      // uint32: CTU generations this scratch slot has seen (validates CU-cache entries)
 #define VXD_SCRATCH_BYTES (VXD_OFF_META + 256)

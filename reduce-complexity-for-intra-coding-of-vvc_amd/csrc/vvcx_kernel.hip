@@ -149,7 +149,16 @@ struct Tables {                    // constant tables staged once per workgroup 
 #define RC_LIST 320
 // per-wave scratch that the rate estimator (pending bin list) and the dependent quantiser (decisions, path nodes) use at different times
 #define DQ_TAB_INTS (21 * 6 + 3 * 12 * 2 + 4)
-struct WaveRc { uint16_t binbuf[RC_LIST]; uint8_t binsort[RC_LIST + 8]; };
+#ifndef VXD_RC_MATCH
+#define VXD_RC_MATCH 1        // the bins of a round grouped by a lane match on the context id (nine ballots per 64 bins) and replayed from a mask, instead of one loop iteration per distinct context
+#endif
+#if VXD_RC_MATCH
+// the estimator's pending bins; behind them the bytes that keep WaveMem at the size from which the batched trellis, which lays its items over all of it, counts the
+// items a wave takes (dq_trellis_phase: 11 / 8 / 4 of 16 / 64 / 256 positions; 9 / 7 / 3 without them)
+struct WaveRc { uint16_t binbuf[RC_LIST]; uint8_t trellis_room[RC_LIST + 8]; };
+#else
+struct WaveRc { uint16_t binbuf[RC_LIST]; uint8_t binsort[RC_LIST + 8]; };      // binsort: the bins sorted by context
+#endif
 // the dependent quantiser lays its per-item areas (last-position offsets, decisions, template rows) over the same bytes and on into tmp / slot behind them
 // (wave_depquant_batch: 240 + 2 * positions bytes per item), so the scratch is sized by the rate estimator's lists alone
 struct alignas(16) WaveScratch { WaveRc rc; };
@@ -666,8 +675,8 @@ __device__ void residual_coding(Cab &cb, const int16_t *coeff, int w, int h, int
 //      (CL/ContextModelling.h:107-199), which of {sig, gt1, par, gt2} it codes and with which contexts, its position in the
 //      bin sequence (ballot prefix sums; the regular-bin budget is a prefix condition) and its bypass bit count.  Which context
 //      a bin uses never depends on the adaptive state, so the bins are *emitted* as (ctx, bin) pairs without touching a model;
-//  (3) the adaptive models: bins of different contexts are independent chains.  The list is grouped by context (ballot per
-//      distinct context), lane t then replays segment t in order (BinProbModel_Std::estFracBitsUpdate), all chains in parallel.
+//  (3) the adaptive models: bins of different contexts are independent chains.  rc_chain finds, 64 bins at a time, the lanes that share a
+//      context; one lane per context replays its bins in order (BinProbModel_Std::estFracBitsUpdate), all chains in parallel.
 __device__ inline int lane_prefix(unsigned long long m)       // set bits of m below this lane
 {
   return (int) __builtin_amdgcn_mbcnt_hi((unsigned) (m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) m, 0u));
@@ -689,10 +698,70 @@ __device__ inline int rem_abs_len(unsigned bins, unsigned rice)   // bit count o
   return (int) (5 + prefix + suffix);
 }
 #define RC_MAXJ 5             // pending list holds at most RC_MAXJ * 64 bins
+#if VXD_RC_MATCH
+static_assert(NCTX <= 512, "rc_chain matches context ids on nine bits");
+// The adaptive models of one round: returns this lane's share of the round's fractional bits.  64 bins at a time, lane = place in coding order: nine ballots, one per bit of
+// the context id, leave every lane with the set of lanes that use its context; the lowest lane of a set replays the set's bins from the low end (ascending lane = coding
+// order; the bin values are one more ballot, so a step reads nothing but the fractional-bit table).  A context that goes on in the next 64 bins finds its models in L.ctxs.
+__device__ __noinline__ unsigned rc_chain(int ci, int wv, int nb, int lane)
+{
+  nb = uni(nb); ci = uni(ci); wv = uni(wv);
+  Ctx *c = &L.ctxs[ci]; const uint16_t *bb = L.wm[wv].ws.rc.binbuf;
+  unsigned bits = 0;
+#ifdef VVCX_STAMP_RC
+  int st_ctx = 0;
+#endif
+  for (int base = 0; base < nb; base += 64) {
+    const bool valid = base + lane < nb;
+    const unsigned e = valid ? bb[base + lane] : 0u;
+    const unsigned ctx = e >> 1;
+    unsigned long long same = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < 9; b++) {
+      const unsigned long long m = __ballot((ctx >> b) & 1);
+      same &= ((ctx >> b) & 1) ? m : ~m;
+    }
+    const unsigned long long binm = __ballot(e & 1);
+    const unsigned blo = (unsigned) binm, bhi = (unsigned) (binm >> 32);
+    const bool owner = valid && lane_prefix(same) == 0;
+#ifdef VVCX_STAMP_RC
+    st_ctx += __popcll(__ballot(owner));
+#endif
+    if (owner) {
+      unsigned a = c->s0[ctx], b = c->s1[ctx];
+      const int rate = L.t.ctx_rate[ctx];
+      const int r0 = 2 + ((rate >> 2) & 3), r1 = 3 + r0 + (rate & 3);
+      const unsigned i0 = (0x7fffu >> r0) & 0x7FE0u, i1 = (0x7fffu >> r1) & 0x7FFEu;
+      // the only loop-carried chain is the state update: the fractional-bit lookup of a step is consumed one step later, so no LDS latency sits on it
+      unsigned mlo = (unsigned) same, mhi = (unsigned) (same >> 32), acc = 0, pend = 0;
+      do {
+        const bool lo = mlo != 0;
+        const unsigned mm = lo ? mlo : mhi, low = mm & (0u - mm);
+        const unsigned bin = ((lo ? blo : bhi) & low) != 0;
+        if (lo) mlo ^= low; else mhi ^= low;
+        acc += pend;
+        pend = BIN_FRAC((a + b) >> 8, bin);
+        a -= (a >> r0) & 0x7FE0u; b -= (b >> r1) & 0x7FFEu;
+        if (bin) { a += i0; b += i1; }
+      } while (mlo | mhi);
+      c->s0[ctx] = (uint16_t) a; c->s1[ctx] = (uint16_t) b;
+      bits += acc + pend;
+    }
+    wave_sync();
+  }
+#ifdef VVCX_STAMP_RC
+  if (VTX == 0) { PROF(16) += 1; PROF(17) += (unsigned long long) nb; PROF(18) += (unsigned long long) st_ctx; if ((unsigned long long) nb > PROF(19)) PROF(19) = (unsigned long long) nb; if ((unsigned long long) st_ctx > PROF(20)) PROF(20) = (unsigned long long) st_ctx; }
+#endif
+  return bits;
+}
+#else
 __device__ __noinline__ void rc_chain(int ci, int wv, int nb, int lane, unsigned long long &bits)
 {
   nb = uni(nb); ci = uni(ci); wv = uni(wv);
   Ctx *c = &L.ctxs[ci]; const uint16_t *bb = L.wm[wv].ws.rc.binbuf; uint8_t *sorted = L.wm[wv].ws.rc.binsort;
+#ifdef VVCX_STAMP_RC
+  int st_ctx = 0;
+#endif
   int ctxv[RC_MAXJ]; unsigned binv[RC_MAXJ]; unsigned long long rem[RC_MAXJ];
 #pragma unroll
   for (int j = 0; j < RC_MAXJ; j++) {
@@ -720,6 +789,9 @@ __device__ __noinline__ void rc_chain(int ci, int wv, int nb, int lane, unsigned
       if (++nseg == 64) break;
     }
     if (nseg == 0) break;
+#ifdef VVCX_STAMP_RC
+    st_ctx += nseg;
+#endif
     wave_sync();
     if (lane < nseg) {
       unsigned a = c->s0[myctx], b = c->s1[myctx];
@@ -743,7 +815,11 @@ __device__ __noinline__ void rc_chain(int ci, int wv, int nb, int lane, unsigned
     wave_sync();
     if (nseg < 64) break;
   }
+#ifdef VVCX_STAMP_RC
+  if (VTX == 0) { PROF(16) += 1; PROF(17) += (unsigned long long) nb; PROF(18) += (unsigned long long) st_ctx; if ((unsigned long long) nb > PROF(19)) PROF(19) = (unsigned long long) nb; if ((unsigned long long) st_ctx > PROF(20)) PROF(20) = (unsigned long long) st_ctx; }
+#endif
 }
+#endif
 template <bool SMALL>
 __device__ __noinline__ void residual_coding_wave(Cab &cb, int lev_off, const int16_t *coeff_g, int w, int h, int is_chroma, int lane, int zo = 0)
 {
@@ -762,7 +838,7 @@ __device__ __noinline__ void residual_coding_wave(Cab &cb, int lev_off, const in
   const long long q1 = STAMP();
   long long qe = 0, qc = 0;
   const int wv = uni(VTX >> 6);
-  uint16_t *bb = L.wm[wv].ws.rc.binbuf; uint8_t *sorted = L.wm[wv].ws.rc.binsort;
+  uint16_t *bb = L.wm[wv].ws.rc.binbuf;
   const int lcg = geo.lcg, cgSize = 1 << lcg;
   const int zw = imin(32, w), zh = imin(32, h), wg = geo.wg, hg = geo.hg;
   const unsigned long long sigGroups = pre.sig_groups, sigRaster = pre.sig_raster;
@@ -865,7 +941,11 @@ __device__ __noinline__ void residual_coding_wave(Cab &cb, int lev_off, const in
     regBins -= used; nb += tot;
     wave_sync();
     const long long e1 = STAMP();
+#if VXD_RC_MATCH
+    mybits += rc_chain(cb.ci, wv, nb, lane);
+#else
     rc_chain(cb.ci, wv, nb, lane, mybits);
+#endif
     nb = 0;
     qe += e1 - e0; qc += STAMP() - e1;
   }
@@ -2398,6 +2478,9 @@ template <bool SMALL> __device__ __noinline__ void stage_b_loop_mts(const VxPara
 //   B1-B3 the same for the (candidate, explicit MTS pair) items that survived the pruning.
 // A wave keeps the best (cost, candidate, transform) item it evaluated parked like stage_b_loop does: the winner of the reference's two nested strict-<
 // loops is the lexicographic minimum of (cost, list position, transform order), which is the minimum of one of the waves.
+#ifndef VXD_DQ_ONE_LIST
+#define VXD_DQ_ONE_LIST 0     // 1: the side-by-side batch of a round (DST-VII beside DCT-II, lfnstIdx 2 beside 1) starts at the wave behind the first batch's last chunk, so that the two are dealt out as one list, instead of at wave 1 whatever the first batch took.  Trellis rounds 3.70 -> 3.32 * 10^11 thread-0 clocks, A3 1.47 -> 1.55, and 0.3 % fewer CTU/s: the idle wave shortens the stream, the CU issues the same instructions
+#endif
 template <bool SMALL>
 __device__ void dq_trellis_phase(uint8_t *scratch, int n, int P, int total, int w, int h, int zo, int wave, int lane, int lfnst = 0, int item0 = 0, int abs0 = 0, int wave_shift = 0)
 {
@@ -2480,8 +2563,10 @@ __device__ __noinline__ void stage_b_rounds(uint8_t *scratch, int wave, int lane
     __syncthreads();
     const long long q1 = STAMP();
     if (!specUse) dq_trellis_phase<SMALL>(scratch, nA, P, total, w, h, psMts, wave, lane, psLf);
-    if (specGen) dq_trellis_phase<SMALL>(scratch, nA, P, total, w, h, 1, wave, lane, 0, nA, 32, 1);
-    if (specGen2) dq_trellis_phase<SMALL>(scratch, nA, P, total, w, h, 0, wave, lane, 2, nA, 32, 1);
+    // (with five to eight candidates of 256 to 511 positions the first batch is two chunks: a second batch from wave 1 gives wave 1 two serial trellis calls and wave 3 none)
+    const int ipwB = imin(16, (int) sizeof(WaveMem) / (240 + 2 * total)), specShift = VXD_DQ_ONE_LIST ? ((nA + ipwB - 1) / ipwB) % NW : 1;
+    if (specGen) dq_trellis_phase<SMALL>(scratch, nA, P, total, w, h, 1, wave, lane, 0, nA, 32, specShift);
+    if (specGen2) dq_trellis_phase<SMALL>(scratch, nA, P, total, w, h, 0, wave, lane, 2, nA, 32, specShift);
     if (tsEarly && wave >= 2) {
       for (int i = wave - 2; i < nA; i += 2) {
         const int sa = wave_ts_fwd(org, poolPred + (size_t) i * P, poolCoef + (size_t) (48 + i) * P, w, h, bd, lane);
@@ -2662,6 +2747,15 @@ __device__ __noinline__ void stage_b_rounds(uint8_t *scratch, int wave, int lane
 #ifdef VVCX_STAMP_PASS
     // diagnostic build: per kind of pass (lfnstIdx 0 / 1 / 2 without MTS, then the MTS passes of transform groups 0..3) the number of chunks and the clocks of the trellis round
     if (VTX == 0) { const int kind = psMts ? 3 + psGrp : psLf; PROF(16 + kind) += 1; PROF(23 + kind) += (unsigned long long) (q2 - q1); }
+    // lfnstIdx 0 rounds in which some wave ran two trellis calls: how many, their clocks, and
+    // the clocks of those in which both batches together have at most NW chunks, so that dealing them out as one list would leave every wave one call
+    if (VTX == 0 && !psMts && psLf == 0) {
+      const int ipw_ = imin(16, (int) sizeof(WaveMem) / (240 + 2 * total)), nch = (nA + ipw_ - 1) / ipw_;
+      const int n1 = specUse ? 0 : nch, n2 = (specGen || specGen2) ? nch : 0;
+      int worst = 0;
+      for (int wv = 0; wv < NW; wv++) { int k = 0; for (int i = 0; i < n1; i++) k += i % NW == wv; for (int i = 0; i < n2; i++) k += (i + (VXD_DQ_ONE_LIST ? n1 : 1)) % NW == wv; worst = imax(worst, k); }
+      if (worst >= 2) { PROF(30) += 1; PROF(47) += (unsigned long long) (q2 - q1); if (n1 + n2 <= NW) PROF(33) += (unsigned long long) (q2 - q1); }
+    }
 #endif
     // ---- per candidate: DCT-II, then its MTS items in transform order, strict < (xRecurIntraCodingLumaQT 3579-3616)
     if ((int) VTX < nA) {
@@ -2837,6 +2931,9 @@ __device__ inline int ict_inv(int c, int mode, int k)
 }
 __device__ inline long long wave_sum_i64(long long v) { return (long long) wave_sum_u64((unsigned long long) v); }
 
+#ifndef VXD_CHROMA_CTX_SNAP
+#define VXD_CHROMA_CTX_SNAP 1  // the models behind a mode's winning variant taken from where its pricing left them (kept in the stream's scratch while joint candidates use the wave's working set) instead of coding the variant once more
+#endif
 template <bool SMALL>
 __device__ __noinline__ void chroma_rd_rounds(uint8_t *scratch, int wave, int lane, int w, int h)
 {
@@ -2892,6 +2989,12 @@ __device__ __noinline__ void chroma_rd_rounds(uint8_t *scratch, int wave, int la
     int16_t *recb = SMALL ? L.wm[wave].slot : slot_rec(scratch, 2 * P, wave, cur), *levb = SMALL ? L.wm[wave].slot + BUF : slot_lev(scratch, 2 * P, wave, cur);
     unsigned long long dist = 0; int cbfs[2] = { 0, 0 };
     double compCost = 0; int jccr = 0;
+#if VXD_CHROMA_CTX_SNAP
+    // [0] the wave's models behind the separately coded pair, saved when the first joint candidate takes the working set; [1] behind the best joint candidate so far.
+    // Every lane reads back the words it wrote.
+    uint32_t *snap = (uint32_t *) (scratch + VXD_OFF_JCTX + (size_t) wave * 2 * VXD_CTXSNAP);
+    int snapped = 0;
+#endif
     if (have) {
       { uint32_t *d = (uint32_t *) &L.ctxs[CI_W(wave)]; const uint32_t *s_ = (const uint32_t *) &L.ctxs[CI_CUR]; for (int e = lane; e < NCTX; e += 64) d[e] = s_[e]; }
       for (int e = lane; e < P; e += 64) { recb[e] = poolPred[(size_t) (2 * c) * P + e]; levb[e] = poolCoef[(size_t) (2 * c) * P + e]; }
@@ -2982,6 +3085,9 @@ __device__ __noinline__ void chroma_rd_rounds(uint8_t *scratch, int wave, int la
           }
           sCb = wave_sum_u64(sCb); sCr = wave_sum_u64(sCr);
           const unsigned long long dJ = (unsigned long long) (p.dist_weight[0] * (double) sCb) + (unsigned long long) (p.dist_weight[1] * (double) sCr);
+#if VXD_CHROMA_CTX_SNAP
+          if (!snapped) { const uint32_t *s_ = (const uint32_t *) &L.ctxs[CI_W(wave)]; for (int e = lane; e < NCTX; e += 64) snap[e] = s_[e]; snapped = 1; }
+#endif
           { uint32_t *d = (uint32_t *) &L.ctxs[CI_W(wave)]; const uint32_t *s_ = (const uint32_t *) &L.ctxs[CI_CUR]; for (int e = lane; e < NCTX; e += 64) d[e] = s_[e]; }
           wave_sync();
           Cab cb; cb.ci = CI_W(wave); cb.bits = 0;
@@ -2992,6 +3098,9 @@ __device__ __noinline__ void chroma_rd_rounds(uint8_t *scratch, int wave, int la
           if (cj < compCost) {
             compCost = cj; jccr = mask; bestJDist = dJ;
             for (int e = lane; e < P; e += 64) { brec[e] = jres[e]; brec[P + e] = jout[e]; blev[e] = jlev[e]; }
+#if VXD_CHROMA_CTX_SNAP
+            { const uint32_t *s_ = (const uint32_t *) &L.ctxs[CI_W(wave)]; for (int e = lane; e < NCTX; e += 64) snap[NCTX + e] = s_[e]; }      // (the estimator ends behind a wave_sync)
+#endif
           }
           wave_sync();
         }
@@ -3001,6 +3110,16 @@ __device__ __noinline__ void chroma_rd_rounds(uint8_t *scratch, int wave, int la
         }
         wave_sync();
       }
+#if VXD_CHROMA_CTX_SNAP
+      // the contexts after the winning variant (4152-4170).  Coding the winner once more from the TU's start contexts repeats, bin for bin, what priced it: the separate
+      // pair (Cb cbf, Cb levels, Cr cbf, flag 0, Cr levels) or the joint candidate (both cbfs, flag 1, the joint levels), and neither the decoder half of wave_code_block
+      // nor a trellis writes the models it is handed.  So the state is the working set as it stands, unless joint candidates used it since
+      if (snapped) {
+        const uint32_t *s_ = snap + (jccr ? NCTX : 0); uint32_t *d = (uint32_t *) &L.ctxs[CI_W(wave)];
+        for (int e = lane; e < NCTX; e += 64) d[e] = s_[e];
+        wave_sync();
+      }
+#else
       if (jccrOn) {                                         // the contexts after the winning variant (4152-4170): replayed from the TU's start contexts
         { uint32_t *d = (uint32_t *) &L.ctxs[CI_W(wave)]; const uint32_t *s_ = (const uint32_t *) &L.ctxs[CI_CUR]; for (int e = lane; e < NCTX; e += 64) d[e] = s_[e]; }
         wave_sync();
@@ -3017,6 +3136,7 @@ __device__ __noinline__ void chroma_rd_rounds(uint8_t *scratch, int wave, int la
         }
         wave_sync();
       }
+#endif
       double cost = 0;
       {                    // 1611-1621: contexts not reset; xGetIntraFracBitsQT(chroma)
         Cab cb; cb.ci = CI_W(wave); cb.bits = 0;
@@ -4008,7 +4128,7 @@ __device__ __attribute__((always_inline)) inline void control_step(const VxParam
     const int d = L.d;
 #if VVCX_STAMP
     const long long tph = STAMP(); const int phs = f.phase;
-#if !defined(VVCX_STAMP_DQ) && !defined(VVCX_STAMP_ISP) && !defined(VVCX_STAMP_PASS)
+#if !defined(VVCX_STAMP_DQ) && !defined(VVCX_STAMP_ISP) && !defined(VVCX_STAMP_PASS) && !defined(VVCX_STAMP_RC)
     struct PhStamp { long long t; int ph; __device__ ~PhStamp() { const int slot = ph < 12 ? 16 + ph : ph == PH_EXIT2 ? 1 : ph == PH_A3_DONE ? 28 : ph == PH_PASS ? 29 : ph == PH_NEXT_PASS ? 31 : 47; PROF(slot) += (unsigned long long) (STAMP() - t); PROF(30) += 1; } } phstamp = { tph, phs };
 #endif
 #endif

@@ -34,7 +34,12 @@ if os.environ.get("VVCX_STAMP_DQ"):
 if os.environ.get("VVCX_STAMP_ISP"):
     print("ISP wave 0: candidates %d  sub-partitions %d  whole candidate %.3e | refs + prediction %.3e  forward transform %.3e  trellis %.3e  dequant + inverse + SSE %.3e  rate %.3e" % (pr[22], pr[23], pr[21], pr[19], pr[16], pr[17], pr[18], pr[20]))
     print("ISP controller: begin + sort %.3e  next-mode %.3e (%d calls)  result replay %.3e  batch building %.3e (%d batches)" % (pr[24], pr[27], pr[28], pr[26], pr[25], pr[29]))
+if os.environ.get("VVCX_STAMP_RC"):
+    c = max(1.0, pr[16])
+    ns = tc * tr      # the profile is summed over the streams: of the per-stream maxima only their mean is left
+    print("rc_chain wave0: rounds %d  bins %.3e (%.1f per round, mean over %d streams of the stream's maximum %.1f)  contexts %.3e (%.1f per round, mean of the streams' maxima %.1f; counted per 64 bins by the lane match)" % (pr[16], pr[17], pr[17] / c, ns, pr[19] / ns, pr[18], pr[18] / c, pr[20] / ns))
 if os.environ.get("VVCX_STAMP_PASS"):
     kinds = ["lfnst 0", "lfnst 1", "lfnst 2", "mts grp 0", "mts grp 1", "mts grp 2", "mts grp 3"]
     for i, k in enumerate(kinds):
         print("pass %-10s chunks %9d  trellis round clocks %.3e  (%.0f per chunk)" % (k, pr[16 + i], pr[23 + i], pr[23 + i] / max(1.0, pr[16 + i])))
+    print("lfnst 0 rounds in which a wave ran two trellis calls: %d of %d, clocks %.3e of %.3e; of those with at most four chunks in both batches together: clocks %.3e" % (pr[30], pr[16], pr[47], pr[23], pr[33]))
