@@ -212,7 +212,8 @@ float vvcx_last_deblock_ms(const vvcx_handle *h);
  * 2 merge; type: for a new CTU 0..3 = edge class 0 / 90 / 135 / 45 degrees, 4 = band offset, for a merge 0 = from the CTU to the left, 1 = from the CTU above (which must be
  * in the same tile); band = band position (0..31); offset[4] = the four coded offsets (edge: full valley, half valley, half peak, full peak; band: the four bands from the
  * band position), multiplied by 2^log2_offset_scale.  lf_across_tiles = pps loop_filter_across_bricks_enabled_flag.  The parameter DECISION (EncSampleAdaptiveOffset) is
- * vvcx_sao_statistics_bound_frames + vvcx_sao_decide below.  In the reference's order this follows vvcx_deblock_bound_frames. */
+ * vvcx_sao_statistics_bound_frames + vvcx_sao_decide below, or vvcx_sao_decide_resident (both halves on the device; vvcx_sao_bound_frames_resident then filters without
+ * the parameters crossing to the host and back).  In the reference's order this follows vvcx_deblock_bound_frames. */
 typedef struct vvcx_sao_param { int8_t mode, type, band, offset[4]; } vvcx_sao_param;
 int   vvcx_sao_bound_frames(vvcx_handle *h, const vvcx_sao_param *prm, int lf_across_tiles, int log2_offset_scale, void *hip_stream);
 float vvcx_last_sao_ms(const vvcx_handle *h);
@@ -233,6 +234,28 @@ float vvcx_last_sao_stats_ms(const vvcx_handle *h);
  * Parity with the reference is unpinned (the unit does not compile in this environment). */
 int   vvcx_sao_decide(int pic_w, int pic_h, int bit_depth, int tile_cols, int tile_rows, int slice_qp, const double *lambda, int log2_offset_scale,
                       const int64_t *stats, vvcx_sao_param *prm);
+/* ---- the same decision on the device, from statistics that STAY in device memory (csrc/vvcx_sao_decide.hip).  Call order on bound pictures:
+ *   ... -> vvcx_deblock_bound_frames -> vvcx_sao_decide_resident -> vvcx_sao_bound_frames_resident -> vvcx_alf_statistics_resident -> ...
+ * vvcx_sao_decide_resident runs the statistics kernel of vvcx_sao_statistics_bound_frames on the bound (completely coded, deblocked) pictures without the copy to the
+ * host, then two decision kernels: one prices every (CTU, component, type) - the offset search, its distortion, the bypass bins - with one lane per (component, type,
+ * class); one walks the CTUs of each picture in raster order with the two context models (one wave per picture) and chooses among the priced candidates and the two merge
+ * candidates.  The result is vvcx_sao_decide's, bit for bit (fp64 cost arithmetic in the same order of operations; that host code is what the tests compare with, and like
+ * it the decision is not pinned to the reference encoder).  The slice QP of the context initialisation is the handle's.  Two things stay in device memory: the resolved
+ * filter table (merges resolved, offsets scaled) that vvcx_sao_bound_frames_resident reads, and the coded parameters.  prm[frame][ctu][component] (host memory, may be
+ * NULL) receives the coded parameters, 21 bytes per CTU - what vvcx_rewrite_payload_bound_frames takes.  Works on an LMCS slice (after vvcx_lmcs_inverse_reco, else
+ * VVCX_ERR_STATE): the handle remembers the caller's own luma plane beside the forward-mapped copy, and the statistics are measured against it, as the reference restores
+ * the true original in front of the loop filters.  VVCX_ERR_ARG: a lambda that is not > 0, an offset scale outside 0..4; VVCX_ERR_STATE: nothing bound, a CTU not coded.
+ * vvcx_last_sao_stats_ms / vvcx_last_sao_decide_ms: HIP-event times of the statistics kernel and of the two decision kernels of the last call.
+ * vvcx_sao_bound_frames_resident: the copy and filter kernels of vvcx_sao_bound_frames on the resident table, lf_across_tiles as given to the decision.  The decision is
+ * valid until a call touches the bound pictures or the buffers: binding, compressing, vvcx_lmcs_inverse_reco, deblocking, either SAO filter call (a second pass would
+ * filter filtered samples), the ALF filter, vvcx_sao_statistics_bound_frames.  VVCX_ERR_STATE without a valid decision. */
+int   vvcx_sao_decide_resident(vvcx_handle *h, int lf_across_tiles, const double lambda[3], int log2_offset_scale, vvcx_sao_param *prm, void *hip_stream);
+int   vvcx_sao_bound_frames_resident(vvcx_handle *h, void *hip_stream);
+float vvcx_last_sao_decide_ms(const vvcx_handle *h);
+/* the same kernels on one picture in host memory (uint16 planes, stride = plane width; prm[ctu][component]): uploads the planes, gathers the statistics, decides.  Needs no
+ * handle; the form the decision kernels are tested through. */
+int   vvcx_sao_decide_picture(int pic_w, int pic_h, int bit_depth, int tile_cols, int tile_rows, int slice_qp, const double lambda[3], int log2_offset_scale,
+                              int lf_across_tiles, const uint16_t *const org[3], const uint16_t *const rec[3], vvcx_sao_param *prm, int device);
 /* the same filter on one picture in host memory (uint16 planes, stride = plane width, filtered in place; prm[ctu][component]): needs no handle */
 int   vvcx_sao_picture(int pic_w, int pic_h, int bit_depth, int tile_cols, int tile_rows, const vvcx_sao_param *prm, int lf_across_tiles, int log2_offset_scale,
                        uint16_t *y, uint16_t *cb, uint16_t *cr, int device);
@@ -261,6 +284,9 @@ int   vvcx_alf_picture(int pic_w, int pic_h, int bit_depth, const vvcx_alf_aps *
 /* ---- the encoder side of ALF (EL/EncAdaptiveLoopFilter.cpp).  Call order of the loop-filter stage on bound pictures:
  *   vvcx_deblock_bound_frames -> vvcx_sao_statistics_bound_frames -> vvcx_sao_decide -> vvcx_sao_bound_frames
  *   -> vvcx_alf_statistics_bound_frames -> vvcx_alf_decide -> vvcx_alf_bound_frames
+ * or, with both decisions from statistics that stay in device memory (on an LMCS slice vvcx_lmcs_inverse_reco comes in front of the deblocking),
+ *   ... -> vvcx_deblock_bound_frames -> vvcx_sao_decide_resident -> vvcx_sao_bound_frames_resident -> vvcx_alf_statistics_resident -> vvcx_alf_decide_resident
+ *   -> vvcx_alf_bound_frames
  * and, for the bitstream, ... -> vvcx_alf_decide -> vvcx_rewrite_payload_bound_frames -> vvcx_get_payload (the rewrite reads no samples: before or after the filter calls).
  *
  * ≙ EncAdaptiveLoopFilter::deriveStatsForFiltering (EL/EncAdaptiveLoopFilter.cpp:2650-2745; getBlkStats 2746-2843, calcCovariance 2844-2965, m_alfWSSD off): the content of

@@ -6,4 +6,4 @@ from .sharding import frames_of_rank, units_of_rank, tile_ctus, tile_bounds, tim
 from .vvcx import distortion_batch, ctx_init, cabac_code_bins, rd_cost_batch, scan_order, transform_quant_batch, PRED_CASE_DTYPE  # noqa: F401
 from .forest import forest_from_sklearn, save_forest, load_forest, check_forest  # noqa: F401
 from .vvcx import depquant_batch, lfnst_depquant_batch, depquant_items  # noqa: F401
-from .vvcx import alf_picture, alf_statistics_picture, alf_decide, alf_stat_sizes, sao_picture, sao_decide  # noqa: F401
+from .vvcx import alf_picture, alf_statistics_picture, alf_decide, alf_stat_sizes, sao_picture, sao_decide, sao_decide_picture  # noqa: F401

@@ -41,6 +41,8 @@ extern "C" __global__ void vvcx_sao_kernel_u8(VxSaoParams p);
 extern "C" __global__ void vvcx_sao_kernel_u16(VxSaoParams p);
 extern "C" __global__ void vvcx_sao_stats_kernel_u8(VxSaoStatParams p);
 extern "C" __global__ void vvcx_sao_stats_kernel_u16(VxSaoStatParams p);
+extern "C" __global__ void vvcx_sao_cand_kernel(VxSaoDecideParams p);
+extern "C" __global__ void vvcx_sao_chain_kernel(VxSaoDecideParams p);
 extern "C" __global__ void vvcx_alf_copy_kernel_u8(VxAlfParams p);
 extern "C" __global__ void vvcx_alf_copy_kernel_u16(VxAlfParams p);
 extern "C" __global__ void vvcx_alf_kernel_u8(VxAlfParams p);
@@ -78,6 +80,8 @@ static int fail(int code, const char *fmt, ...)
 
 // device buffers of the ALF decision passes (vvcx_alf_eval.hip): frame sums, error tables, the CTU mask and the candidates of a call
 struct AlfWork { DevBuf<long long> sum_l, sum_c, err_l, err_c; DevBuf<uint8_t> mask; DevBuf<VxAlfLumaCand> lc; DevBuf<VxAlfChromaCand> cc; };
+// device buffers of the SAO decision kernels (vvcx_sao_decide.hip): candidate records, the coded parameters, the estimator's bit table
+struct SaoWork { DevBuf<VxSaoCand> cand; DevBuf<VxSaoSyn> syn; DevBuf<uint32_t> frac; };
 
 struct vvcx_handle {
   vvcx_cfg cfg; vvcx_slice sl; bool have_slice;
@@ -113,6 +117,10 @@ struct vvcx_handle {
   DevBuf<uint8_t> sao_tmp_d; DevBuf<VxSaoEntry> sao_tab_d; DevBuf<uint8_t> sao_tile_d;      // vvcx_sao_bound_frames: picture copy, resolved parameters, CTU -> tile
   DevBuf<uint8_t> db_edges_d;      // vvcx_deblock_bound_frames: one edge byte per unit, map and direction
   DevBuf<long long> sao_stat_d; float last_sao_stats_ms;      // vvcx_sao_statistics_bound_frames
+  // vvcx_sao_decide_resident: sao_tab_d / sao_tile_d hold the decision of the bound pictures (for vvcx_sao_bound_frames_resident) while no call has touched the
+  // pictures or these buffers since; the decision kernels' buffers; on an LMCS slice the frame records whose org[0] is the caller's own (unmapped) luma
+  bool sao_res_valid; int sao_res_lf; SaoWork sao_work; hipEvent_t ev2; float last_sao_decide_ms;
+  DevBuf<VxFrameDev> frames_org_d;
   DevBuf<VxAlfFrame> alf_tab_d; DevBuf<VxAlfCtu> alf_ctu_d; float last_alf_ms;      // vvcx_alf_bound_frames: per-frame tables and per-CTU choices (the picture copy is the SAO one)
   DevBuf<long long> alf_stat_luma_d, alf_stat_chroma_d; float last_alf_stats_ms;      // vvcx_alf_statistics_bound_frames
   // vvcx_alf_statistics_resident: what alf_stat_*_d hold (frame range, bins, chroma) while no call has touched the pictures since; the decision passes' buffers
@@ -241,7 +249,7 @@ extern "C" int vvcx_create(const vvcx_cfg *cfg, vvcx_handle **out)
     (void) hipMemcpy(h->payload_cap_d.p, h->payload_cap.data(), nstream * 4, hipMemcpyHostToDevice);
     (void) hipMemset(h->arith_d.p, 0, nstream * 32);
   }
-  (void) hipEventCreate(&h->ev0); (void) hipEventCreate(&h->ev1);
+  (void) hipEventCreate(&h->ev0); (void) hipEventCreate(&h->ev1); (void) hipEventCreate(&h->ev2);
   *out = h;
   return VVCX_OK;
 }
@@ -251,7 +259,7 @@ extern "C" void vvcx_destroy(vvcx_handle *h)
   if (!h) return;
   if (h->pending) (void) hipStreamSynchronize(h->pend_stream);      // first: a launch still in flight reads and writes what is freed below
   (void) hipHostFree(h->pend_res);
-  (void) hipEventDestroy(h->ev0); (void) hipEventDestroy(h->ev1);
+  (void) hipEventDestroy(h->ev0); (void) hipEventDestroy(h->ev1); (void) hipEventDestroy(h->ev2);
   delete h;                                     // frees every device buffer
 }
 
@@ -407,7 +415,7 @@ static void ctx_from_reference_order(const uint16_t *s0, const uint16_t *s1, uin
 extern "C" int vvcx_bind_frames(vvcx_handle *h, const vvcx_frame *frames, int n)
 {
   NOT_PENDING(h);
-  if (h) h->alf_res_valid = false;      // the resident ALF statistics no longer describe the bound pictures
+  if (h) h->alf_res_valid = h->sao_res_valid = false;      // the resident ALF statistics / SAO decision no longer describe the bound pictures
   if (!h || !frames) return fail(VVCX_ERR_ARG, "null argument");
   ON_DEVICE(h->cfg.device);
   if (n < 1 || n > h->cfg.max_frames) return fail(VVCX_ERR_ARG, "n_frames %d outside 1..%d", n, h->cfg.max_frames);
@@ -437,6 +445,10 @@ extern "C" int vvcx_bind_frames(vvcx_handle *h, const vvcx_frame *frames, int n)
     HIPCHK(h->lmcs_org_d.reserve(need));
     HIPCHK(h->lmcs_lut_d.reserve(2 * 1024));
     HIPCHK(hipMemcpy(h->lmcs_lut_d.p, h->lmcs_fwd, 2048, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(h->lmcs_lut_d.p + 1024, h->lmcs_inv, 2048, hipMemcpyHostToDevice));
+    // the records with the caller's own luma: the SAO encoder measures against the true original, which the reference restores in front of the loop filters
+    // (a second record array of the handle; the search's records get the mapped copy below)
+    HIPCHK(h->frames_org_d.reserve((size_t) n));
+    HIPCHK(hipMemcpy(h->frames_org_d.p, h->frames_h.data(), sizeof(VxFrameDev) * (size_t) n, hipMemcpyHostToDevice));
     size_t off = 0;
     for (int f = 0; f < n; f++) {
       VxFrameDev &d = h->frames_h[(size_t) f];
@@ -523,7 +535,7 @@ static void stream_params(vvcx_handle *h, VxParams &p)
 extern "C" int vvcx_submit_ctus(vvcx_handle *h, const vvcx_ctu_task *tasks, int n, void *hip_stream)
 {
   NOT_PENDING(h);
-  if (h) h->alf_res_valid = false;      // the resident ALF statistics no longer describe the bound pictures
+  if (h) h->alf_res_valid = h->sao_res_valid = false;      // the resident ALF statistics / SAO decision no longer describe the bound pictures
   if (h && (h->cfg.tools & VVCX_TOOL_FAST) && !h->f_ntrees) return fail(VVCX_ERR_STATE, "VVCX_TOOL_FAST needs vvcx_set_forest before the first CTU");
   if (!h || (!tasks && n) || n < 0) return fail(VVCX_ERR_ARG, "bad argument");
   if (n == 0) { h->pending = true; h->pend_n = 0; h->pend_stream = (hipStream_t) hip_stream; h->pend_src.clear(); h->pend_next = h->next_idx; return VVCX_OK; }   // nothing to code: an empty submission, not an error
@@ -742,7 +754,7 @@ static int require_all_coded(const vvcx_handle *h, const char *what)
 extern "C" int vvcx_lmcs_inverse_reco(vvcx_handle *h, void *hip_stream)
 {
   NOT_PENDING(h);
-  if (h) h->alf_res_valid = false;      // the resident ALF statistics no longer describe the bound pictures
+  if (h) h->alf_res_valid = h->sao_res_valid = false;      // the resident ALF statistics / SAO decision no longer describe the bound pictures
   if (!h) return fail(VVCX_ERR_ARG, "null handle");
   if (!h->n_frames || !h->have_slice || !h->lmcs_on) return fail(VVCX_ERR_STATE, "no bound frames coded with an LMCS slice");
   if (!h->lmcs_lut_d.p) return fail(VVCX_ERR_STATE, "the bound pictures were not prepared with an LMCS slice: vvcx_bind_frames after vvcx_set_slice");
@@ -767,7 +779,7 @@ extern "C" int vvcx_lmcs_inverse_reco(vvcx_handle *h, void *hip_stream)
 extern "C" int vvcx_deblock_bound_frames(vvcx_handle *h, int beta_offset_div2, int tc_offset_div2, void *hip_stream)
 {
   NOT_PENDING(h);
-  if (h) h->alf_res_valid = false;      // the resident ALF statistics no longer describe the bound pictures
+  if (h) h->alf_res_valid = h->sao_res_valid = false;      // the resident ALF statistics / SAO decision no longer describe the bound pictures
   if (!h) return fail(VVCX_ERR_ARG, "null handle");
   if (!h->n_frames || !h->have_slice) return fail(VVCX_ERR_STATE, "no bound frames / slice");
   if (const int rc = require_all_coded(h, "deblocking")) return rc;
@@ -864,7 +876,7 @@ static void sao_launch(VxSaoParams &p, int n_frames, size_t bps, hipStream_t str
 extern "C" int vvcx_sao_bound_frames(vvcx_handle *h, const vvcx_sao_param *prm, int lf_across_tiles, int log2_offset_scale, void *hip_stream)
 {
   NOT_PENDING(h);
-  if (h) h->alf_res_valid = false;      // the resident ALF statistics no longer describe the bound pictures
+  if (h) h->alf_res_valid = h->sao_res_valid = false;      // the resident ALF statistics / SAO decision no longer describe the bound pictures
   if (!h || !prm) return fail(VVCX_ERR_ARG, "null argument");
   if (!h->n_frames || !h->have_slice) return fail(VVCX_ERR_STATE, "no bound frames / slice");
   if (log2_offset_scale < 0 || log2_offset_scale > 4) return fail(VVCX_ERR_ARG, "log2 offset scale outside 0..4");
@@ -922,6 +934,7 @@ extern "C" float vvcx_last_sao_ms(const vvcx_handle *h) { return h ? h->last_sao
 extern "C" int vvcx_sao_statistics_bound_frames(vvcx_handle *h, int lf_across_tiles, int64_t *stats, void *hip_stream)
 {
   NOT_PENDING(h);
+  if (h) h->sao_res_valid = false;      // sao_stat_d / sao_tile_d are reused: a resident SAO decision is gone
   if (!h || !stats) return fail(VVCX_ERR_ARG, "null argument");
   if (!h->n_frames || !h->have_slice) return fail(VVCX_ERR_STATE, "no bound frames / slice");
   if (const int rc = require_all_coded(h, "the SAO statistics")) return rc;
@@ -996,6 +1009,14 @@ public:
     else if (first) bypass(2);
   }
   static int max_q(int bd) { return (1 << (std::min(bd, 10) - 5)) - 1; }      // SampleAdaptiveOffset::getMaxOffsetQVal
+  // the two models as the device form of this estimator (vvcx_sao_decide.hip) starts from them: states, adaptation shifts
+  void export_models(VxSaoDecideParams &p) const
+  {
+    for (int k = 0; k < 2; k++) {
+      const int rate = VX_CTX_RATE_REF[kFirst + k];
+      p.s0[k] = s0_[k]; p.s1[k] = s1_[k]; p.r0[k] = 2 + ((rate >> 2) & 3); p.r1[k] = 3 + p.r0[k] + (rate & 3);
+    }
+  }
 private:
   static const int kFirst = VX_CTX_REF_SaoMergeFlag;    // Ctx::SaoMergeFlag in the reference's flat order (ContextSetCfg); SaoTypeIdx follows
   uint16_t s0_[2], s1_[2];
@@ -1176,6 +1197,146 @@ extern "C" int vvcx_sao_decide(int pic_w, int pic_h, int bit_depth, int tile_col
   return VVCX_OK;
 }
 
+// ---- the same decision on the device (vvcx_sao_decide.hip), from statistics that stay in device memory: the candidate kernel prices every (CTU, component, type), the
+// chain kernel walks the CTUs of each picture with the two context models.  What it leaves: the resolved filter table (exactly what sao_resolve builds from the coded
+// parameters) and the coded parameters, both in device memory; 21 bytes per CTU cross to the host when the caller asks for them.
+static void sao_tile_table(int cw, int chh, int tc, int tr, std::vector<uint8_t> &tile)
+{
+  tile.resize((size_t) cw * chh);
+  for (int a = 0; a < cw * chh; a++) {
+    int tx = 0, ty = 0;
+    for (int i = 0; i < tc; i++) if (a % cw >= (i * cw) / tc) tx = i;
+    for (int i = 0; i < tr; i++) if (a / cw >= (i * chh) / tr) ty = i;
+    tile[(size_t) a] = (uint8_t) (ty * tc + tx);
+  }
+}
+// buffers of a decision over n_frames pictures of nctu CTUs: every allocation of the call, in front of its first launch
+static int sao_decide_reserve(SaoWork &w, DevBuf<long long> &stat_d, DevBuf<VxSaoEntry> &tab_d, DevBuf<uint8_t> &tile_d, int n_frames, int nctu)
+{
+  const size_t n = (size_t) n_frames * nctu;
+  HIPCHK(stat_d.reserve(n * 3 * 5 * 64)); HIPCHK(tab_d.reserve(n * 3)); HIPCHK(tile_d.reserve((size_t) nctu));
+  HIPCHK(w.cand.reserve(n * 15)); HIPCHK(w.syn.reserve(n * 3));
+  bool grew = false;
+  HIPCHK(w.frac.reserve(512, &grew));
+  if (grew) HIPCHK(hipMemcpy(w.frac.p, VX_BIN_FRAC_BITS, 512 * sizeof(uint32_t), hipMemcpyHostToDevice));
+  return VVCX_OK;
+}
+// the statistics kernel on `frames` into stat_d, then the two decision kernels; ev0 .. ev1 .. ev2 (optional) around the two halves
+static int sao_decide_launch(const VxFrameDev *frames, size_t bps, int chroma, SaoWork &w, long long *stat_d, VxSaoEntry *tab_d, const uint8_t *tile_d, int n_frames,
+                             int pic_w, int pic_h, int bit_depth, int slice_qp, const double *lambda, int log2_offset_scale, int lf_across_tiles, hipStream_t stream,
+                             hipEvent_t ev0, hipEvent_t ev1, hipEvent_t ev2)
+{
+  const int cw = (pic_w + 127) / 128, chh = (pic_h + 127) / 128, nctu = cw * chh;
+  HIPCHK(hipMemsetAsync(stat_d, 0, (size_t) n_frames * nctu * 3 * 5 * 64 * sizeof(long long), stream));
+  VxSaoStatParams sp; memset(&sp, 0, sizeof sp);
+  sp.frames = frames; sp.tile_of_ctu = tile_d; sp.out = stat_d;
+  sp.pic_w = pic_w; sp.pic_h = pic_h; sp.ctus_w = cw; sp.ctus_h = chh; sp.bit_depth = bit_depth; sp.chroma = chroma; sp.lf_across_tiles = lf_across_tiles != 0;
+  if (ev0) HIPCHK(hipEventRecord(ev0, stream));
+  const dim3 grid((unsigned) nctu, 3u, (unsigned) n_frames);
+  if (bps == 1) hipLaunchKernelGGL(vvcx_sao_stats_kernel_u8, grid, dim3(256), 0, stream, sp);
+  else hipLaunchKernelGGL(vvcx_sao_stats_kernel_u16, grid, dim3(256), 0, stream, sp);
+  HIPCHK(hipGetLastError());
+  if (ev1) HIPCHK(hipEventRecord(ev1, stream));
+  VxSaoDecideParams p; memset(&p, 0, sizeof p);
+  p.stats = stat_d; p.cands = w.cand.p; p.tile_of_ctu = tile_d; p.frac_bits = w.frac.p; p.table = tab_d; p.syn = w.syn.p;
+  for (int k = 0; k < 3; k++) p.lambda[k] = lambda[k];
+  p.ctus_w = cw; p.ctus_h = chh; p.bit_depth = bit_depth; p.step = log2_offset_scale;
+  SaoRate rate; rate.init(slice_qp); rate.export_models(p);
+  hipLaunchKernelGGL(vvcx_sao_cand_kernel, dim3((unsigned) nctu, (unsigned) n_frames), dim3(192), 0, stream, p);
+  hipLaunchKernelGGL(vvcx_sao_chain_kernel, dim3((unsigned) n_frames), dim3(64), 0, stream, p);
+  HIPCHK(hipGetLastError());
+  if (ev2) HIPCHK(hipEventRecord(ev2, stream));
+  return VVCX_OK;
+}
+static_assert(sizeof(VxSaoSyn) == sizeof(vvcx_sao_param), "device copy of the C-ABI record");
+extern "C" int vvcx_sao_decide_resident(vvcx_handle *h, int lf_across_tiles, const double lambda[3], int log2_offset_scale, vvcx_sao_param *prm, void *hip_stream)
+{
+  NOT_PENDING(h);
+  if (h) h->sao_res_valid = false;
+  if (!h || !lambda) return fail(VVCX_ERR_ARG, "null argument");
+  if (!h->n_frames || !h->have_slice) return fail(VVCX_ERR_STATE, "no bound frames / slice");
+  if (log2_offset_scale < 0 || log2_offset_scale > 4 || !(lambda[0] > 0) || !(lambda[1] > 0) || !(lambda[2] > 0)) return fail(VVCX_ERR_ARG, "vvcx_sao_decide_resident: offset scale / lambdas");
+  if (const int rc = require_all_coded(h, "the SAO decision")) return rc;
+  if (h->lmcs_on && !h->lmcs_inverted) return fail(VVCX_ERR_STATE, "LMCS slice: vvcx_lmcs_inverse_reco first (the loop filters work in the original domain)");
+  const int cw = h->ctus_w, chh = h->ctus_h, nctu = cw * chh;
+  if (cw > VXD_SAO_MAX_CTUS_W || h->ntiles > 255) return fail(VVCX_ERR_UNSUPPORTED, "vvcx_sao_decide_resident: %d CTU columns / %d tiles", cw, h->ntiles);
+  std::vector<uint8_t> tile;
+  sao_tile_table(cw, chh, h->cfg.tile_cols, h->cfg.tile_rows, tile);
+  ON_DEVICE(h->cfg.device);
+  hipStream_t stream = (hipStream_t) hip_stream;
+  if (const int rc = sao_decide_reserve(h->sao_work, h->sao_stat_d, h->sao_tab_d, h->sao_tile_d, h->n_frames, nctu)) return rc;
+  HIPCHK(hipMemcpyAsync(h->sao_tile_d.p, tile.data(), (size_t) nctu, hipMemcpyHostToDevice, stream));
+  // on an LMCS slice the search's records carry the forward-mapped luma: the statistics read the records with the caller's own plane
+  const VxFrameDev *frames = h->lmcs_on ? h->frames_org_d.p : h->frames_d.p;
+  if (const int rc = sao_decide_launch(frames, h->cfg.bit_depth == 8 ? 1 : 2, h->cfg.chroma, h->sao_work, h->sao_stat_d.p, h->sao_tab_d.p, h->sao_tile_d.p, h->n_frames,
+                                       h->cfg.pic_w, h->cfg.pic_h, h->cfg.bit_depth, h->sl.qp, lambda, log2_offset_scale, lf_across_tiles, stream, h->ev0, h->ev1, h->ev2)) return rc;
+  if (prm) HIPCHK(hipMemcpyAsync(prm, h->sao_work.syn.p, (size_t) h->n_frames * nctu * 3 * sizeof(VxSaoSyn), hipMemcpyDeviceToHost, stream));
+  HIPCHK(hipStreamSynchronize(stream));             // (the host tile table above must outlive its copy)
+  HIPCHK(hipEventElapsedTime(&h->last_sao_stats_ms, h->ev0, h->ev1));
+  HIPCHK(hipEventElapsedTime(&h->last_sao_decide_ms, h->ev1, h->ev2));
+  h->sao_res_valid = true; h->sao_res_lf = lf_across_tiles != 0;
+  return VVCX_OK;
+}
+extern "C" float vvcx_last_sao_decide_ms(const vvcx_handle *h) { return h ? h->last_sao_decide_ms : 0.f; }
+// the filter of vvcx_sao_bound_frames with the table the decision left in sao_tab_d
+extern "C" int vvcx_sao_bound_frames_resident(vvcx_handle *h, void *hip_stream)
+{
+  NOT_PENDING(h);
+  if (!h) return fail(VVCX_ERR_ARG, "null handle");
+  const bool valid = h->sao_res_valid;
+  h->alf_res_valid = h->sao_res_valid = false;      // the pictures change: a second pass would filter filtered samples
+  if (!h->n_frames || !h->have_slice) return fail(VVCX_ERR_STATE, "no bound frames / slice");
+  if (!valid) return fail(VVCX_ERR_STATE, "no resident SAO decision (vvcx_sao_decide_resident), or a call has touched the bound pictures since");
+  const int cw = h->ctus_w, chh = h->ctus_h;
+  ON_DEVICE(h->cfg.device);
+  hipStream_t stream = (hipStream_t) hip_stream;
+  const size_t bps = h->cfg.bit_depth == 8 ? 1 : 2, ny = (size_t) h->cfg.pic_w * h->cfg.pic_h, per_frame = ny + 2 * (ny >> 2);
+  HIPCHK(h->sao_tmp_d.reserve((size_t) h->n_frames * per_frame * bps));
+  VxSaoParams p; memset(&p, 0, sizeof p);
+  p.frames = h->frames_d.p; p.table = h->sao_tab_d.p; p.tile_of_ctu = h->sao_tile_d.p; p.tmp = h->sao_tmp_d.p; p.tmp_frame = per_frame; p.tmp_comp[0] = 0; p.tmp_comp[1] = ny; p.tmp_comp[2] = ny + (ny >> 2);
+  p.pic_w = h->cfg.pic_w; p.pic_h = h->cfg.pic_h; p.ctus_w = cw; p.ctus_h = chh; p.bit_depth = h->cfg.bit_depth; p.chroma = h->cfg.chroma; p.lf_across_tiles = h->sao_res_lf;
+  HIPCHK(hipEventRecord(h->ev0, stream));
+  sao_launch(p, h->n_frames, bps, stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(h->ev1, stream));
+  HIPCHK(hipStreamSynchronize(stream));
+  HIPCHK(hipEventElapsedTime(&h->last_sao_ms, h->ev0, h->ev1));
+  return VVCX_OK;
+}
+// the decision kernels on one picture in host memory (uint16 planes, stride = plane width): the leaf entry the decision is pinned through
+extern "C" int vvcx_sao_decide_picture(int pic_w, int pic_h, int bit_depth, int tile_cols, int tile_rows, int slice_qp, const double lambda[3], int log2_offset_scale,
+                                       int lf_across_tiles, const uint16_t *const org[3], const uint16_t *const rec[3], vvcx_sao_param *prm, int device)
+{
+  if (!lambda || !org || !rec || !prm) return fail(VVCX_ERR_ARG, "null argument");
+  for (int c = 0; c < 3; c++) if (!org[c] || !rec[c]) return fail(VVCX_ERR_ARG, "null plane");
+  if (pic_w < 8 || pic_h < 8 || (pic_w & 7) || (pic_h & 7) || pic_w > 16384 || pic_h > 16384 || bit_depth < 8 || bit_depth > 12 || tile_cols < 1 || tile_rows < 1 ||
+      tile_cols > (pic_w + 127) / 128 || tile_rows > (pic_h + 127) / 128 || tile_cols * tile_rows > 255 || log2_offset_scale < 0 || log2_offset_scale > 4 ||
+      !(lambda[0] > 0) || !(lambda[1] > 0) || !(lambda[2] > 0))
+    return fail(VVCX_ERR_ARG, "vvcx_sao_decide_picture: picture size / bit depth / tiles / offset scale / lambdas");
+  const int cw = (pic_w + 127) / 128, chh = (pic_h + 127) / 128, nctu = cw * chh;
+  std::vector<uint8_t> tile;
+  sao_tile_table(cw, chh, tile_cols, tile_rows, tile);
+  ON_DEVICE(device);
+  DevBuf<uint16_t> planes; DevBuf<VxFrameDev> frame; SaoWork w; DevBuf<long long> stat_d; DevBuf<VxSaoEntry> tab_d; DevBuf<uint8_t> tile_d;
+  const size_t ny = (size_t) pic_w * pic_h, ncs = ny >> 2, per = ny + 2 * ncs;
+  HIPCHK(planes.alloc(2 * per)); HIPCHK(frame.alloc(1));
+  if (const int rc = sao_decide_reserve(w, stat_d, tab_d, tile_d, 1, nctu)) return rc;
+  VxFrameDev fd; memset(&fd, 0, sizeof fd);
+  const size_t off[3] = { 0, ny, ny + ncs };
+  for (int c = 0; c < 3; c++) {
+    fd.org[c] = planes.p + off[c]; fd.rec[c] = planes.p + per + off[c]; fd.stride[c] = c ? pic_w >> 1 : pic_w;
+    HIPCHK(hipMemcpy(planes.p + off[c], org[c], (c ? ncs : ny) * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(planes.p + per + off[c], rec[c], (c ? ncs : ny) * 2, hipMemcpyHostToDevice));
+  }
+  HIPCHK(hipMemcpy(frame.p, &fd, sizeof fd, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(tile_d.p, tile.data(), tile.size(), hipMemcpyHostToDevice));
+  if (const int rc = sao_decide_launch(frame.p, 2, 1, w, stat_d.p, tab_d.p, tile_d.p, 1, pic_w, pic_h, bit_depth, slice_qp, lambda, log2_offset_scale, lf_across_tiles,
+                                       0, nullptr, nullptr, nullptr)) return rc;
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(prm, w.syn.p, (size_t) nctu * 3 * sizeof(VxSaoSyn), hipMemcpyDeviceToHost));
+  return VVCX_OK;
+}
+
 // ---- adaptive loop filter (≙ AdaptiveLoopFilter::ALFProcess, CL/AdaptiveLoopFilter.cpp:205-383) with the caller's parameter sets: the per-class tables of every frame's
 // slice are built here (≙ reconstructCoeffAPSs 385-418 / reconstructCoeff 420-608, JVET_O0669 form), the kernels (vvcx_alf.hip) classify and filter.
 static int alf_clip_value(int chroma, int bit_depth, int idx)      // create() 633-654
@@ -1247,7 +1408,7 @@ static void alf_launch(VxAlfParams &p, int n_frames, size_t bps, hipStream_t str
 extern "C" int vvcx_alf_bound_frames(vvcx_handle *h, const vvcx_alf_aps *aps, int n_aps, const vvcx_alf_slice *slices, const vvcx_alf_ctu *ctus, void *hip_stream)
 {
   NOT_PENDING(h);
-  if (h) h->alf_res_valid = false;      // the resident ALF statistics no longer describe the bound pictures
+  if (h) h->alf_res_valid = h->sao_res_valid = false;      // the resident ALF statistics / SAO decision no longer describe the bound pictures
   if (!h || !slices || !ctus || (n_aps > 0 && !aps)) return fail(VVCX_ERR_ARG, "null argument");
   if (!h->n_frames || !h->have_slice) return fail(VVCX_ERR_STATE, "no bound frames / slice");
   if (const int rc = require_all_coded(h, "ALF")) return rc;

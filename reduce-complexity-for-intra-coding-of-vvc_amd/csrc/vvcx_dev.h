@@ -189,6 +189,26 @@ struct VxRewriteParams {
   int32_t trace_cap, pad_;
 };
 
+// SAO encoder decision on the device (vvcx_sao_decide.hip).  One candidate record per (frame, CTU, component, type): what the offset search keeps of the statistics
+struct VxSaoCand {
+  long long dist;                 // SSE change of the kept offsets (scaled) on the CTU's statistics
+  int32_t bypass;                 // bypass bins of the component's syntax with these parameters; the two context-coded bins are the chain's
+  int8_t off[4], band, pad_[7];   // coded offsets: full valley, half valley, half peak, full peak / the four bands from the band position
+};
+struct VxSaoDecideParams {
+  const long long *stats;         // [frame][ctu][3][5 types][count | diff][32], as VxSaoStatParams::out
+  VxSaoCand *cands;               // [frame][ctu][3][5]
+  const uint8_t *tile_of_ctu;     // [ctu]
+  const uint32_t *frac_bits;      // [512]: the estimator's bits of a bin per state (VX_BIN_FRAC_BITS)
+  VxSaoEntry *table;              // out [frame][ctu][3]: merges resolved, offsets scaled (what the filter reads)
+  VxSaoSyn *syn;                  // out [frame][ctu][3]: the coded parameters
+  double lambda[3];
+  int32_t ctus_w, ctus_h, bit_depth, step;
+  uint16_t s0[2], s1[2];          // the models SaoMergeFlag, SaoTypeIdx at the start of a picture (I-slice initialisation at the slice QP)
+  int32_t r0[2], r1[2];           // their adaptation shifts
+};
+#define VXD_SAO_MAX_CTUS_W 128    // CTU columns the chain kernel keeps a row of reconstructed parameters for (pictures up to 16384 wide)
+
 // per-stream scratch layout (bytes)
 #define VXD_STORE_REC   (128 * 128 * 2)
 #define VXD_STORE_UNITS (32 * 32 * (int) sizeof(VxUnit))

@@ -149,6 +149,19 @@ def sao_decide(stats, width, height, bit_depth, lambdas, slice_qp, tile_cols=1, 
     return prm
 
 
+def sao_decide_picture(org, rec, bit_depth, lambdas, slice_qp, tile_cols=1, tile_rows=1, log2_offset_scale=0, lf_across_tiles=1, device=0, lib_path=None):
+    """vvcx_sao_decide_picture: statistics and the SAO decision of one picture in host memory, both on the device -> int8 [ctus, 3, 7] parameters as sao_decide returns them"""
+    L = load_library(lib_path)
+    o = [np.ascontiguousarray(p.astype(np.uint16)) for p in org]; r = [np.ascontiguousarray(p.astype(np.uint16)) for p in rec]
+    h, w = r[0].shape
+    lam = np.ascontiguousarray(lambdas, np.float64)
+    prm = np.zeros((((w + 127) // 128) * ((h + 127) // 128), 3, 7), np.int8)
+    op = (C.c_void_p * 3)(*[p.ctypes.data for p in o]); rp = (C.c_void_p * 3)(*[p.ctypes.data for p in r])
+    L.vvcx_sao_decide_picture.argtypes = [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int]
+    _chk(L, L.vvcx_sao_decide_picture(w, h, bit_depth, tile_cols, tile_rows, int(slice_qp), lam.ctypes.data, int(log2_offset_scale), int(lf_across_tiles), op, rp, prm.ctypes.data, device))
+    return prm
+
+
 class AlfAps(C.Structure):
     """vvcx_alf_aps: what an ALF parameter set carries (AlfParam of the reference)"""
     _fields_ = [("num_luma_filters", C.c_int32), ("class_to_filter", C.c_uint8 * 25), ("nonlinear_luma", C.c_uint8), ("luma_coeff", (C.c_int16 * 12) * 25), ("luma_clip_idx", (C.c_uint8 * 12) * 25),
@@ -425,6 +438,31 @@ class VvcxEncoder:
         self.L.vvcx_last_sao_stats_ms.argtypes = [C.c_void_p]
         self._chk(self.L.vvcx_sao_statistics_bound_frames(self.h, int(lf_across_tiles), out.ctypes.data, None))
         return out, float(self.L.vvcx_last_sao_stats_ms(self.h))
+
+    def sao_decide_resident(self, lambdas, lf_across_tiles=1, log2_offset_scale=0):
+        """vvcx_sao_decide_resident: statistics and decision of every bound picture on the device; the resolved table stays there for sao_bound_frames_resident ->
+        (int8 [n_frames, ctus, 3, 7] coded parameters as sao_bound_frames takes them, time of the decision kernels in ms; the statistics kernel's: sao_stats_ms)"""
+        lam = np.ascontiguousarray(lambdas, np.float64)
+        prm = np.zeros((self.n_frames, self.ctus_per_frame, 3, 7), np.int8)
+        self.L.vvcx_sao_decide_resident.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        self.L.vvcx_last_sao_decide_ms.restype = C.c_float
+        self.L.vvcx_last_sao_decide_ms.argtypes = [C.c_void_p]
+        self._chk(self.L.vvcx_sao_decide_resident(self.h, int(lf_across_tiles), lam.ctypes.data, int(log2_offset_scale), prm.ctypes.data, None))
+        return prm, float(self.L.vvcx_last_sao_decide_ms(self.h))
+
+    def sao_stats_ms(self):
+        """vvcx_last_sao_stats_ms: HIP-event time of the last SAO statistics kernel of this handle (either route)"""
+        self.L.vvcx_last_sao_stats_ms.restype = C.c_float
+        self.L.vvcx_last_sao_stats_ms.argtypes = [C.c_void_p]
+        return float(self.L.vvcx_last_sao_stats_ms(self.h))
+
+    def sao_bound_frames_resident(self):
+        """vvcx_sao_bound_frames_resident: the SAO filter with the table sao_decide_resident left on the device; returns the kernel time in ms"""
+        self.L.vvcx_sao_bound_frames_resident.argtypes = [C.c_void_p, C.c_void_p]
+        self.L.vvcx_last_sao_ms.restype = C.c_float
+        self.L.vvcx_last_sao_ms.argtypes = [C.c_void_p]
+        self._chk(self.L.vvcx_sao_bound_frames_resident(self.h, None))
+        return float(self.L.vvcx_last_sao_ms(self.h))
 
     def alf_bound_frames(self, prms):
         """vvcx_alf_bound_frames: prms = one dict of synth.alf_test_params' form per bound frame (the parameter sets of the first are the call's); returns the kernel time in ms"""
