@@ -1,4 +1,4 @@
-// vvcx_host.h — what the host code of the library (vvcx_api.hip, vvcx_lmcs.hip) shares: how an entry point selects its device, how a failed HIP call becomes
+// vvcx_host.h — what the host code of the library (vvcx_api*.hip and the files behind them, vvcx_lmcs.hip) shares: how an entry point selects its device, how a failed HIP call becomes
 // VVCX_ERR_DEVICE, and the one type that owns device memory.  Host only: nothing here is seen by a kernel.
 #pragma once
 #include <hip/hip_runtime.h>

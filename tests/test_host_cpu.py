@@ -529,6 +529,139 @@ def test_loop_filters_recover_from_a_failed_device_allocation(emu_so):
     enc.close(); ref.close()
 
 
+_LF_ENTRIES = ("lmcs_inverse_reco", "deblock_bound_frames", "sao_bound_frames", "sao_statistics_bound_frames", "sao_decide_resident", "sao_bound_frames_resident",
+               "alf_bound_frames", "alf_statistics_bound_frames", "alf_statistics_resident", "alf_decide_resident")
+_LF_NO_FRAMES = (-4, b"no bound frames / slice")
+_LF_PENDING = (-4, b"a submitted launch is outstanding: call vvcx_wait_ctus first")
+_LF_NOT_INVERTED = (-4, b"LMCS slice: vvcx_lmcs_inverse_reco first (the loop filters work in the original domain)")
+_LF_NO_SAO = (-4, b"no resident SAO decision (vvcx_sao_decide_resident), or a call has touched the bound pictures since")
+_LF_NO_ALF = (-4, b"no resident ALF statistics (vvcx_alf_statistics_resident), or a call has touched the bound pictures since")
+
+
+def _lf_not_coded(what):
+    return (-4, what + b" needs every CTU of the bound pictures coded (frame 0 tile 0 is not)")
+
+
+# (return code, vvcx_last_error()) of every bound-frame loop-filter entry per handle state, as the library answered before its host file was split
+_LF_MATRIX = {
+    "no frames": dict(
+        lmcs_inverse_reco=(-4, b"no bound frames coded with an LMCS slice"), deblock_bound_frames=_LF_NO_FRAMES, sao_bound_frames=_LF_NO_FRAMES,
+        sao_statistics_bound_frames=_LF_NO_FRAMES, sao_decide_resident=_LF_NO_FRAMES, sao_bound_frames_resident=_LF_NO_FRAMES, alf_bound_frames=_LF_NO_FRAMES,
+        alf_statistics_bound_frames=_LF_NO_FRAMES, alf_statistics_resident=_LF_NO_FRAMES, alf_decide_resident=_LF_NO_ALF),
+    "not coded": dict(
+        lmcs_inverse_reco=(-4, b"no bound frames coded with an LMCS slice"), deblock_bound_frames=_lf_not_coded(b"deblocking"), sao_bound_frames=_lf_not_coded(b"SAO"),
+        sao_statistics_bound_frames=_lf_not_coded(b"the SAO statistics"), sao_decide_resident=_lf_not_coded(b"the SAO decision"), sao_bound_frames_resident=_LF_NO_SAO,
+        alf_bound_frames=_lf_not_coded(b"ALF"), alf_statistics_bound_frames=_lf_not_coded(b"the ALF statistics"),
+        alf_statistics_resident=_lf_not_coded(b"the ALF statistics"), alf_decide_resident=_LF_NO_ALF),
+    "pending": {e: _LF_PENDING for e in _LF_ENTRIES},
+    "lmcs not coded": dict(
+        lmcs_inverse_reco=_lf_not_coded(b"the inverse LMCS mapping (intra prediction reads mapped neighbours)")),
+    "lmcs not inverted": dict(
+        lmcs_inverse_reco=(0, None), deblock_bound_frames=_LF_NOT_INVERTED, sao_bound_frames=_LF_NOT_INVERTED,
+        sao_statistics_bound_frames=(-2, b"SAO statistics of an LMCS slice: the handle keeps the mapped original only"), sao_decide_resident=_LF_NOT_INVERTED,
+        sao_bound_frames_resident=_LF_NO_SAO, alf_bound_frames=_LF_NOT_INVERTED,
+        alf_statistics_bound_frames=(-2, b"ALF statistics of an LMCS slice: the handle keeps the mapped original only"),
+        alf_statistics_resident=(-2, b"ALF statistics of an LMCS slice: the handle keeps the mapped original only"), alf_decide_resident=_LF_NO_ALF),
+}
+
+
+def test_precondition_matrix_of_the_bound_frame_loop_filter_entries(emu_so):
+    """What each bound-frame loop-filter entry answers (return code and the exact vvcx_last_error() bytes) when its handle is not in the state it needs: a slice but no
+    pictures, pictures not coded, a submitted launch not collected, an LMCS slice whose reconstruction is still mapped; and which of them end a resident SAO decision /
+    resident ALF statistics.  The expected values are what the library answered while all of this was one file: the shared preconditions must keep every one of them."""
+    vv = importlib.import_module(PKGNAME + ".vvcx")
+
+    def handle(w, h, bd, tools, sp, planes, lmcs=None):
+        enc = pkg.VvcxEncoder(w, h, bd, tools=tools, lib_path=emu_so)
+        enc.set_slice(sp["qp"], sp["qp_c"], sp["lam"], sp["dist_weight"], lmcs=lmcs)
+        org = [np.ascontiguousarray(p) for p in planes]; rec = [np.zeros_like(p) for p in planes]
+        return enc, ([p.ctypes.data for p in org], [p.ctypes.data for p in rec], [p.shape[1] for p in org]), (org, rec)
+
+    def entries(enc, w, h):
+        """name -> call on one frame's worth of valid arguments -> (return code, message)"""
+        L, hd, nctu = enc.L, enc.h, enc.ctus_per_frame
+        lam = np.array([60.0, 50.0, 50.0])
+        sao = np.zeros((1, nctu, 3, 7), np.int8)
+        sao_stats = np.zeros((1, nctu, 3, 5, 2, 32), np.int64)
+        aps, sl, ctu = vv._alf_args([O.alf_params(6, w, h)])
+        szl, szc = vv.alf_stat_sizes(1)
+        luma = np.zeros((1, nctu, 25, szl), np.int64); chroma = np.zeros((1, nctu, 2, szc), np.int64)
+        o_aps = (vv.AlfAps * 1)(); o_sl = (vv.AlfSlice * 1)(); o_ctu = np.zeros((1, nctu, 6), np.int8)
+        P, I = C.c_void_p, C.c_int
+        calls = dict(
+            lmcs_inverse_reco=(L.vvcx_lmcs_inverse_reco, [P, P], (hd, None)),
+            deblock_bound_frames=(L.vvcx_deblock_bound_frames, [P, I, I, P], (hd, 0, 0, None)),
+            sao_bound_frames=(L.vvcx_sao_bound_frames, [P, P, I, I, P], (hd, sao.ctypes.data, 1, 0, None)),
+            sao_statistics_bound_frames=(L.vvcx_sao_statistics_bound_frames, [P, I, P, P], (hd, 1, sao_stats.ctypes.data, None)),
+            sao_decide_resident=(L.vvcx_sao_decide_resident, [P, I, P, I, P, P], (hd, 1, lam.ctypes.data, 0, None, None)),
+            sao_bound_frames_resident=(L.vvcx_sao_bound_frames_resident, [P, P], (hd, None)),
+            alf_bound_frames=(L.vvcx_alf_bound_frames, [P, P, I, P, P, P], (hd, C.addressof(aps), len(aps), C.addressof(sl), ctu.ctypes.data, None)),
+            alf_statistics_bound_frames=(L.vvcx_alf_statistics_bound_frames, [P, I, I, I, P, P, P], (hd, 0, 1, 1, luma.ctypes.data, chroma.ctypes.data, None)),
+            alf_statistics_resident=(L.vvcx_alf_statistics_resident, [P, I, I, I, P], (hd, 0, 1, 1, None)),
+            alf_decide_resident=(L.vvcx_alf_decide_resident, [P, P, I, I, P, P, P, P], (hd, lam.ctypes.data, 25, 0, C.addressof(o_aps), C.addressof(o_sl), o_ctu.ctypes.data, None)))
+        keep = (lam, sao, sao_stats, aps, sl, ctu, luma, chroma, o_aps, o_sl, o_ctu)
+
+        def run(name, keep=keep):
+            fn, argtypes, args = calls[name]
+            fn.argtypes = argtypes; fn.restype = C.c_int
+            rc = fn(*args)
+            return (rc, None) if rc == 0 else (rc, bytes(L.vvcx_last_error()))
+        return run
+
+    def check(state, run, names=_LF_ENTRIES):
+        for name in names:
+            got = run(name)
+            print(state, name, got)
+            assert got == _LF_MATRIX[state][name], (state, name, got)
+
+    # ---- 64x48, 8 bit
+    w, h = 64, 48
+    planes = pkg.synth_frame(w, h, 0, 8, 7, chroma_texture=0.5)
+    enc, bind, keep = handle(w, h, 8, pkg.TOOLS_DEFAULT, pkg.slice_params(32), planes)
+    run = entries(enc, w, h)
+    check("no frames", run)
+    enc.bind_frames([bind])
+    check("not coded", run)
+    enc.compress_bound_frames()
+    assert enc.submit_ctus([]) == 0                                 # an empty submission is a submission
+    check("pending", run)
+    enc.wait_ctus(0)
+    # what ends a resident SAO decision: every call that changes the pictures, and the SAO statistics (they reuse its buffers); the ALF statistics read only
+    for name, ends in (("deblock_bound_frames", True), ("sao_bound_frames", True), ("alf_bound_frames", True), ("sao_statistics_bound_frames", True),
+                       ("alf_statistics_bound_frames", False), ("alf_statistics_resident", False)):
+        assert run("sao_decide_resident") == (0, None)
+        assert run(name) == (0, None), name
+        got = run("sao_bound_frames_resident")
+        print("after sao_decide_resident +", name, got)
+        assert got == (_LF_NO_SAO if ends else (0, None)), (name, got)
+    assert run("sao_bound_frames_resident") == _LF_NO_SAO           # the filter itself ends it: a second pass would filter filtered samples
+    # the mirror image for the resident ALF statistics: the SAO statistics and the SAO decision read only
+    for name, ends in (("deblock_bound_frames", True), ("sao_bound_frames", True), ("alf_bound_frames", True), ("alf_statistics_bound_frames", True),
+                       ("sao_statistics_bound_frames", False), ("sao_decide_resident", False)):
+        assert run("alf_statistics_resident") == (0, None)
+        assert run(name) == (0, None), name
+        got = run("alf_decide_resident")
+        print("after alf_statistics_resident +", name, got)
+        assert got == (_LF_NO_ALF if ends else (0, None)), (name, got)
+    assert run("sao_decide_resident") == (0, None) and run("alf_statistics_resident") == (0, None)
+    assert run("sao_bound_frames_resident") == (0, None) and run("alf_decide_resident") == _LF_NO_ALF      # the resident SAO filter changes the pictures
+    enc.close()
+    # ---- 16x16, 10 bit, LMCS slice
+    w = h = 16
+    lm = _lmcs_model_10bit()
+    planes = pkg.synth_frame(w, h, 0, 10, 5, chroma_texture=0.8, oriented=20.0, limited=True)
+    enc, bind, keep = handle(w, h, 10, 0xf7b, pkg.slice_params(27, bit_depth=10, dep_quant=True), planes, lmcs=lm)
+    run = entries(enc, w, h)
+    enc.bind_frames([bind])
+    check("lmcs not coded", run, ("lmcs_inverse_reco",))
+    enc.compress_bound_frames()
+    check("lmcs not inverted", run, [e for e in _LF_ENTRIES if e != "lmcs_inverse_reco"])
+    check("lmcs not inverted", run, ("lmcs_inverse_reco",))          # now it runs ...
+    assert run("lmcs_inverse_reco") == (-4, b"the reconstruction has already been mapped back")
+    assert run("deblock_bound_frames") == (0, None) and run("sao_decide_resident") == (0, None)      # ... and the filters accept the pictures
+    enc.close()
+
+
 def test_training_set_dump_on_cpu_emulator_matches_oracle(emu_so):
     """vvcx_enable_training_dump / vvcx_get_training_rows (the fork's GET_TRAINING_SET): every qualifying luma node of the plain full search leaves its 26 features, its
     complexity class and the partition the search chose; the rows equal the oracle's dump (orc_set_training_dump) - all six labels occur - and the search itself is unchanged."""
