@@ -319,7 +319,7 @@ float vvcx_last_alf_stats_ms(const vvcx_handle *h);
  * are several + per coefficient ue(|c|) + 1 sign bit when c != 0; chroma = 1 + ue(0) + the coefficients; an enabled luma CTU costs one bin more than a disabled one
  * (alf_use_aps_flag), a chroma CTU's flag costs the same either way; a component whose gain does not pay for its parameter-set bits stays unfiltered.
  * Not here: the clip-index search for nonlinear filters and the fixed filter sets as candidates (vvcx_alf_decide_resident / vvcx_alf_decide_picture below have both);
- * out of scope: several chroma alternatives, parameter-set reuse across pictures.  Parity with the reference's RD choice is unpinned (the unit does not compile in this environment). */
+ * out of scope here: several chroma alternatives (VVCX_ALF_CHROMA_ALTS of the resident decision has them), parameter-set reuse across pictures.  Parity with the reference's RD choice is unpinned (the unit does not compile in this environment). */
 int   vvcx_alf_decide(int pic_w, int pic_h, int bit_depth, int chroma, int n_bins, const int64_t *luma, const int64_t *chroma_stats,
                       const double lambda[3], int max_luma_filters, vvcx_alf_aps *aps, vvcx_alf_slice *slice, vvcx_alf_ctu *ctus);
 /* ---- the decision from statistics that STAY in device memory, with nonlinear filters and the fixed filter sets (csrc/vvcx_alf_eval.hip).  Call order on bound pictures:
@@ -361,12 +361,48 @@ float vvcx_last_alf_cand_ms(const vvcx_handle *h);
  *   its parameter-set bits the slice carries no luma set (n_luma_aps = 0, CTU sets < 16).
  * With J = sum over CTUs (predicted error + lambda * bits) + lambda * parameter-set bits, the returned decision has by construction J <= J(all off), J <= J(the flags-0
  * decision) and, with VVCX_ALF_FIXED_SETS, J <= J(the best choice among off and the fixed sets): it is the least of these complete decisions and the new-set ones.
- * Out of scope: several chroma alternatives, parameter-set reuse across pictures, parity with EncAdaptiveLoopFilter's RD choice. */
+ * VVCX_ALF_CHROMA_ALTS(n), n = 1..8, OR-ed into flags: up to min(n, 2 * ctus) chroma alternatives (≙ the chroma loop of alfEncoder, EL 1041-1135; getMaxNumAlternativesChroma
+ *   3849).  n = 1 (the value 0) is the decision described above, byte for byte; a handle without chroma ignores the field; luma is never touched.  For n >= 2, per frame:
+ *   D1 = the one-alternative decision above with its cost J1 (0 when chroma stays off).  Then for K = min(n, 2 * ctus) down to 2: the CTUs start in K raster runs, the same
+ *   for Cb and Cr (≙ initCtuAlternativeChroma, EL 3831-3847: label[a] = alt; if ((a + 1) * K >= (alt + 1) * ctus) ++alt), and two steps alternate:
+ *     (a) re-derive: vvcx_alf_chroma_label_sums, then per alternative the quantised least-squares filter of its pooled Cb + Cr sums; with VVCX_ALF_NONLINEAR_CHROMA also the
+ *         clip search on those sums, kept only where its predicted gain over the linear filter exceeds 12 clip bits at the mean chroma lambda (the nonlinear flag is per
+ *         alternative).  An alternative no block carries keeps its previous filter (the zero filter at first);
+ *     (b) assign: vvcx_alf_chroma_assign - per (CTU, component) the cheapest of off and the K alternatives.
+ *   J_K = sum of the chosen costs + mean chroma lambda * (ue(K' - 1) + sum over the used alternatives (1 + coefficient bits + 12 when nonlinear)), K' = the alternatives
+ *   still used; unused ones are dropped and the rest renumbered in ascending order, and the CTUs' alternative bits are then those of the final numbering.  The pair of
+ *   steps is repeated while J falls, K + 1 times at most (2 (K + 1) of the reference's 2 (K + 1) + 1 half-steps, EL 1084); the least J_K seen is kept with its filters and
+ *   labels.  The result is the least of J1 and the J_K, so J_chroma(n) <= J_chroma(1) <= 0 by construction.  It has chroma_aps = 0, 1 <= num_chroma_alt <= min(n, 2 * ctus),
+ *   every alternative used by an enabled (CTU, component), alt[c] < num_chroma_alt and alt[c] = 0 where the flag is 0.  All frames of a call advance in the same device
+ *   calls (a frame whose J stopped falling is carried along), so the number of blocking passes per call does not depend on the frame count: at most the sum over
+ *   K = min(n, 2 * ctus) .. 2 of 2 (K + 1) (84 for K = 8) on top of the one-alternative decision's; the passes read the chroma statistics only.
+ * Out of scope: parameter-set reuse across pictures, clip re-optimisation inside the class merge, parity with EncAdaptiveLoopFilter's RD choice. */
 #define VVCX_ALF_NONLINEAR_LUMA   1
 #define VVCX_ALF_NONLINEAR_CHROMA 2
 #define VVCX_ALF_FIXED_SETS       4
+#define VVCX_ALF_CHROMA_ALTS(n)   (((n) - 1) << 8)
 int   vvcx_alf_decide_resident(vvcx_handle *h, const double lambda[3], int max_luma_filters, int flags, vvcx_alf_aps *aps, vvcx_alf_slice *slices, vvcx_alf_ctu *ctus,
                                void *hip_stream);
+int   vvcx_last_alf_device_calls(const vvcx_handle *h);      /* blocking device passes of the handle's last vvcx_alf_decide_resident */
+/* The two passes of the chroma-alternative iteration on the resident statistics (they need chroma: VVCX_ERR_STATE without it, and when nothing is resident or it is stale).
+ * A label is an alternative 0 .. n_alts - 1 (n_alts = 1..8) or 255 = off; anything else is VVCX_ERR_ARG.
+ * vvcx_alf_chroma_label_sums (≙ getFrameStats per alternative): labels[n][ctus][2] (Cb, Cr) -> sums[n][n_alts][size]: per frame and alternative the element-wise sum of
+ *   the Cb and Cr blocks that carry its label (the two components are pooled); zeros for an alternative no block carries.
+ * vvcx_alf_chroma_assign (≙ the alternative choice of deriveCtbAlfEnableFlags, EL 927-954): cands[n][n_alts]; per (frame, CTU, component c) and alternative a
+ *     cost_a = (double) err_a / 16384. + lambda_c[c] * bits(a, n_alts),      bits(a, K) = 0 for K = 1, else min(a + 1, K - 1)
+ *   with err_a exactly vvcx_alf_candidate_errors' chroma error and bits the truncated-unary length codeAlfCtuAlternative writes (one bit per bin, this project's own
+ *   count); off costs 0.  The candidates are compared in the order off, 0, 1, .. with a strict <: the earliest wins a tie, off wins against a cost of exactly 0.  Product
+ *   and sum are rounded separately (never fused).  labels[n][ctus][2] = the choice, err[n][ctus][2] = its err (0 when off), cost[n] = the chosen costs added by one lane
+ *   in raster order, Cb before Cr - a float64 loop on the host gives the same bits.  Coefficients beyond +-128 and clipping indices >= the gathered bins are VVCX_ERR_ARG.
+ * All arrays are host memory; the calls block.  vvcx_last_alf_sum_ms / _cand_ms report these kernels when they ran last.
+ * vvcx_alf_chroma_alts_picture: the host-plane form (no handle, like vvcx_alf_evaluate_picture).  Either half may be NULL: labels_in -> sums; cands, lambda_c ->
+ * labels_out, err, cost. */
+int   vvcx_alf_chroma_label_sums(vvcx_handle *h, const uint8_t *labels, int n_alts, int64_t *sums, void *hip_stream);
+int   vvcx_alf_chroma_assign(vvcx_handle *h, const vvcx_alf_chroma_cand *cands, int n_alts, const double lambda_c[2], uint8_t *labels, int64_t *err, double *cost,
+                             void *hip_stream);
+int   vvcx_alf_chroma_alts_picture(int pic_w, int pic_h, int bit_depth, int n_bins, const uint16_t *const org[3], const uint16_t *const rec[3], const uint8_t *labels_in,
+                                   const vvcx_alf_chroma_cand *cands, int n_alts, const double lambda_c[2], int64_t *sums, uint8_t *labels_out, int64_t *err, double *cost,
+                                   int device);
 /* the host-plane forms (no handle; org / rec as for vvcx_alf_statistics_picture, chroma planes required): the planes are uploaded, the statistics gathered into temporary
  * device memory, and the same kernels and the same decision code run.  vvcx_alf_evaluate_picture: ctu_on[ctus][3] (may be NULL) -> luma_sum[25][size], chroma_sum[2][size];
  * the candidates -> luma_err[ctus][16 fixed_sets + n_luma], chroma_err[ctus][2][n_chroma] (either pair of outputs may be NULL).  Parity unpinned, as above. */

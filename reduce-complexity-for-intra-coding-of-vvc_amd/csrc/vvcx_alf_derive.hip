@@ -1,6 +1,6 @@
 // vvcx_alf_derive.hip — the host numeric code of ALF behind the C-ABI (include/vvcx.h): the filter tables of the caller's parameter sets, and the filter derivation of
 // the encoder side (vvcx_alf_decide; alf_decide_frames for the decisions whose statistics stay on the device).  The only device work is what alf_decide_frames asks
-// of alf_sums / alf_errors (vvcx_api_loopfilter.hip).
+// of alf_sums / alf_errors and, for several chroma alternatives, of alf_label_sums / alf_assign (vvcx_api_loopfilter.hip).
 #include <stdint.h>
 #include <string.h>
 #include <math.h>
@@ -333,6 +333,110 @@ static void alf_luma_sets(const int64_t *sums, int nb, double lambda, int max_fi
   nl.valid = nl.nonlinear;
 }
 
+// ---- several chroma alternatives (≙ the chroma loop of alfEncoder, EL 1041-1135, in this project's form; include/vvcx.h has the algorithm and the bit count).  For
+// K = k_max .. 2 the CTUs start in K raster runs (≙ initCtuAlternativeChroma, EL 3831-3847) and two steps alternate: the filters of the alternatives from the blocks that
+// carry their label (alf_label_sums), and per (CTU, component) the cheapest of off and the alternatives (alf_assign).  All frames advance in the same device calls; a
+// frame whose J has stopped falling is carried along unchanged.  j1[f] = J of the one-alternative decision already in aps / slices / ctus; a frame is overwritten only
+// where an alternative set has a smaller J.
+struct AlfAltSet { int K, q[8][6], clip[8][6]; bool nl[8]; std::vector<uint8_t> lab; double J; };
+static int alf_alt_bits(int a, int K) { return K == 1 ? 0 : std::min(a + 1, K - 1); }      // codeAlfCtuAlternative: truncated unary, one bit per bin
+static int alf_chroma_alts(AlfRes &r, const double lambda[3], bool nonlinear, int k_max, const double *j1, vvcx_alf_aps *aps, vvcx_alf_slice *slices, vvcx_alf_ctu *ctus)
+{
+  const int n = r.n, nctu = r.nctu, nb = r.nb, nblk = 2 * nctu;
+  const size_t szc = alf_stat_size(nb, 7);
+  const double lamC = .5 * (lambda[1] + lambda[2]), lam_c[2] = { lambda[1], lambda[2] };
+  std::vector<AlfAltSet> best((size_t) n), cur((size_t) n);
+  std::vector<uint8_t> lab((size_t) n * nblk), labOut((size_t) n * nblk), done((size_t) n);
+  std::vector<int64_t> sums((size_t) n * k_max * szc), err((size_t) n * nblk);
+  std::vector<double> cost((size_t) n), prevJ((size_t) n);
+  std::vector<vvcx_alf_chroma_cand> cd((size_t) n * k_max);
+  for (int f = 0; f < n; f++) { best[(size_t) f].K = 0; best[(size_t) f].J = j1[f]; }
+  for (int K = k_max; K >= 2; K--) {
+    for (int f = 0; f < n; f++) {
+      AlfAltSet &c = cur[(size_t) f];
+      c.K = K; memset(c.q, 0, sizeof c.q); memset(c.clip, 0, sizeof c.clip); memset(c.nl, 0, sizeof c.nl);
+      for (int a = 0, alt = 0; a < nctu; a++) {
+        lab[((size_t) f * nctu + a) * 2] = lab[((size_t) f * nctu + a) * 2 + 1] = (uint8_t) alt;
+        if ((a + 1) * K >= (alt + 1) * nctu) ++alt;
+      }
+      done[(size_t) f] = 0; prevJ[(size_t) f] = INFINITY;
+    }
+    for (int it = 0; it < K + 1; it++) {      // two half-steps each: at most 2 (K + 1) of the 2 (K + 1) + 1 the reference allows
+      if (std::find(done.begin(), done.end(), 0) == done.end()) break;
+      // (a) the filters of the alternatives that have blocks; the others keep theirs
+      if (const int rc = alf_label_sums(r, lab.data(), K, sums.data())) return rc;
+      for (int f = 0; f < n; f++) {
+        AlfAltSet &c = cur[(size_t) f];
+        if (!done[(size_t) f]) for (int a = 0; a < K; a++) {
+          const uint8_t *lf = lab.data() + (size_t) f * nblk;
+          if (std::find(lf, lf + nblk, (uint8_t) a) == lf + nblk) continue;
+          const int64_t *blk = sums.data() + ((size_t) f * K + a) * szc;
+          AlfCov s; s.clear(); s.add(blk, nb, 7);
+          alf_quant(s, 6, c.q[a]);
+          memset(c.clip[a], 0, sizeof c.clip[a]); c.nl[a] = false;
+          int qn[6], cn[6];
+          if (nonlinear && alf_clip_search(blk, nb, 7, c.q[a], qn, cn)) {
+            AlfCov g; alf_gather(blk, nb, 7, cn, g);
+            if (s.err_q(c.q[a], 6) - g.err_q(qn, 6) > lamC * 12) {      // the clipped filter where its gain on these sums pays its clip bits
+              for (int k = 0; k < 6; k++) { c.q[a][k] = qn[k]; c.clip[a][k] = cn[k]; }
+              c.nl[a] = true;
+            }
+          }
+        }
+        for (int a = 0; a < K; a++) for (int k = 0; k < 6; k++) {
+          cd[(size_t) f * K + a].coeff[k] = (int16_t) c.q[a][k]; cd[(size_t) f * K + a].clip_idx[k] = (uint8_t) c.clip[a][k];
+        }
+      }
+      // (b) the CTUs' choices among them
+      if (const int rc = alf_assign(r, cd.data(), K, lam_c, labOut.data(), err.data(), cost.data())) return rc;
+      for (int f = 0; f < n; f++) {
+        if (done[(size_t) f]) continue;
+        const AlfAltSet &c = cur[(size_t) f];
+        const uint8_t *lo = labOut.data() + (size_t) f * nblk;
+        int to[8], used = 0, pbits = 0;
+        for (int a = 0; a < K; a++) {
+          to[a] = std::find(lo, lo + nblk, (uint8_t) a) != lo + nblk ? used++ : -1;
+          if (to[a] >= 0) pbits += 1 + alf_coeff_bits(c.q[a], 6) + (c.nl[a] ? 12 : 0);
+        }
+        double J = 0.;
+        if (used) {
+          double ct = cost[(size_t) f];
+          if (used != K) {      // fewer alternatives are left: the CTUs' bits are those of the final numbering
+            ct = 0.;
+            for (int i = 0; i < nblk; i++) if (lo[i] != 255) {
+              const double e = (double) err[(size_t) f * nblk + i] / 16384., b = lam_c[i & 1] * (double) alf_alt_bits(to[lo[i]], used);
+              ct = ct + (e + b);
+            }
+          }
+          J = ct + lamC * (alf_ue_bits(used - 1) + pbits);
+          if (J < best[(size_t) f].J) {
+            AlfAltSet &b = best[(size_t) f];
+            b.K = used; b.J = J; b.lab.assign(lo, lo + nblk);
+            for (int i = 0; i < nblk; i++) if (lo[i] != 255) b.lab[(size_t) i] = (uint8_t) to[lo[i]];
+            for (int a = 0; a < K; a++) if (to[a] >= 0) { memcpy(b.q[to[a]], c.q[a], sizeof c.q[a]); memcpy(b.clip[to[a]], c.clip[a], sizeof c.clip[a]); b.nl[to[a]] = c.nl[a]; }
+          }
+        }
+        if (!(J < prevJ[(size_t) f])) { done[(size_t) f] = 1; continue; }
+        prevJ[(size_t) f] = J;
+        memcpy(lab.data() + (size_t) f * nblk, lo, (size_t) nblk);
+      }
+    }
+  }
+  for (int f = 0; f < n; f++) {
+    const AlfAltSet &b = best[(size_t) f];
+    if (!b.K) continue;
+    vvcx_alf_aps &ap = aps[f]; vvcx_alf_ctu *cu = ctus + (size_t) f * nctu;
+    slices[f].chroma_aps = 0; ap.num_chroma_alt = b.K;
+    memset(ap.nonlinear_chroma, 0, sizeof ap.nonlinear_chroma); memset(ap.chroma_coeff, 0, sizeof ap.chroma_coeff); memset(ap.chroma_clip_idx, 0, sizeof ap.chroma_clip_idx);
+    for (int a = 0; a < b.K; a++) {
+      ap.nonlinear_chroma[a] = b.nl[a];
+      for (int k = 0; k < 6; k++) { ap.chroma_coeff[a][k] = (int16_t) b.q[a][k]; ap.chroma_clip_idx[a][k] = (uint8_t) b.clip[a][k]; }
+    }
+    for (int i = 0; i < nblk; i++) { const bool on = b.lab[(size_t) i] != 255; cu[i >> 1].flag[1 + (i & 1)] = on; cu[i >> 1].alt[i & 1] = on ? b.lab[(size_t) i] : 0; }
+  }
+  return VVCX_OK;
+}
+
 int alf_decide_frames(AlfRes &r, bool chroma, const double lambda[3], int max_luma_filters, int flags, vvcx_alf_aps *aps, vvcx_alf_slice *slices, vvcx_alf_ctu *ctus)
 {
   const int n = r.n, nctu = r.nctu, nb = r.nb;
@@ -347,6 +451,7 @@ int alf_decide_frames(AlfRes &r, bool chroma, const double lambda[3], int max_lu
   std::vector<vvcx_alf_chroma_cand> cc((size_t) n * 2);
   std::vector<int> qc((size_t) n * 6), qcn((size_t) n * 6), clipc((size_t) n * 6); std::vector<uint8_t> cnl((size_t) n, 0);
   AlfLumaSet none; none.valid = false;
+  std::vector<double> j1c((size_t) n, 0.);      // J of each frame's one-alternative chroma decision (0: chroma off)
   for (int f = 0; f < n; f++) {
     alf_luma_sets(sl.data() + (size_t) f * 25 * szl, nb, lambda[0], max_luma_filters, false, set[(size_t) f * 4], none);
     alf_expand(set[(size_t) f * 4], lc[(size_t) f]);
@@ -473,11 +578,14 @@ int alf_decide_frames(AlfRes &r, bool chroma, const double lambda[3], int max_lu
         useN = Jn < J;
       }
       if (lin || useN) {
+        j1c[(size_t) f] = useN ? Jn : J;
         sl_o.chroma_aps = 0; ap.num_chroma_alt = 1; ap.nonlinear_chroma[0] = useN;
         for (int k = 0; k < 6; k++) { ap.chroma_coeff[0][k] = (int16_t) (useN ? qn[k] : q[k]); ap.chroma_clip_idx[0][k] = (uint8_t) (useN ? clipc[(size_t) f * 6 + k] : 0); }
         for (int i = 0; i < 2 * nctu; i++) cu[i >> 1].flag[1 + (i & 1)] = useN ? ec[(size_t) i * nc1 + 1] < 0 : maskA[((size_t) f * nctu + (i >> 1)) * 3 + 1 + (i & 1)];
       }
     }
   }
+  const int k_max = chroma ? std::min((flags >> 8) + 1, 2 * nctu) : 1;      // ≙ getMaxNumAlternativesChroma, EL 3849
+  if (k_max >= 2) return alf_chroma_alts(r, lambda, nlC, k_max, j1c.data(), aps, slices, ctus);
   return VVCX_OK;
 }

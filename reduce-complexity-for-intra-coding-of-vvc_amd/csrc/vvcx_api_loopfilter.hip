@@ -543,6 +543,7 @@ int alf_sums(AlfRes &r, const uint8_t *ctu_on, int64_t *luma, int64_t *chroma)
   if (wantC) HIPCHK(hipMemcpyAsync(chroma, w.sum_c.p, nch * sizeof(long long), hipMemcpyDeviceToHost, r.stream));
   HIPCHK(hipStreamSynchronize(r.stream));
   if (r.ev0) HIPCHK(hipEventElapsedTime(&r.sum_ms, r.ev0, r.ev1));
+  r.calls++;
   if (chroma && !wantC) memset(chroma, 0, nch * sizeof(int64_t));
   return VVCX_OK;
 }
@@ -579,14 +580,73 @@ int alf_errors(AlfRes &r, int fixed_sets, const vvcx_alf_luma_cand *lc, int n_lu
     if (wantC) HIPCHK(hipMemcpyAsync(chroma_err, w.err_c.p, nce * sizeof(long long), hipMemcpyDeviceToHost, r.stream));
     HIPCHK(hipStreamSynchronize(r.stream));
     if (r.ev0) HIPCHK(hipEventElapsedTime(&r.cand_ms, r.ev0, r.ev1));
+    r.calls++;
   }
   if (n_chroma && !wantC) memset(chroma_err, 0, nce * sizeof(int64_t));      // no chroma statistics
   return VVCX_OK;
 }
 
+// the chroma blocks of every frame summed per label (vvcx_alf_chroma_label_sum_kernel): Cb and Cr pooled, zeros for a label no block carries
+int alf_label_sums(AlfRes &r, const uint8_t *labels, int n_alts, int64_t *sums)
+{
+  if (!r.chroma) return fail(VVCX_ERR_STATE, "ALF chroma alternatives: the statistics have no chroma");
+  if (!labels || !sums) return fail(VVCX_ERR_ARG, "null argument");
+  if (n_alts < 1 || n_alts > VX_ALF_MAX_ALTS) return fail(VVCX_ERR_ARG, "ALF chroma alternatives: %d (1..%d)", n_alts, VX_ALF_MAX_ALTS);
+  const size_t nlab = (size_t) r.n * r.nctu * 2, szc = alf_stat_size(r.nb, 7), ns = (size_t) r.n * n_alts * szc;
+  for (size_t i = 0; i < nlab; i++) if (labels[i] >= n_alts && labels[i] != VX_ALF_LABEL_OFF)
+    return fail(VVCX_ERR_ARG, "ALF chroma alternatives: label %d of block %d (0..%d, or 255 = off)", labels[i], (int) i, n_alts - 1);
+  AlfWork &w = *r.w;
+  HIPCHK(w.lab.reserve(nlab)); HIPCHK(w.lab_sum.reserve(ns));
+  HIPCHK(hipMemcpyAsync(w.lab.p, labels, nlab, hipMemcpyHostToDevice, r.stream));
+  VxAlfLabelSumParams p; memset(&p, 0, sizeof p);
+  p.chroma = r.chroma; p.labels = w.lab.p; p.out = w.lab_sum.p; p.nctu = r.nctu; p.n_alts = n_alts; p.size_c = szc;
+  const dim3 grid((unsigned) ((szc + 255) / 256), 1u, (unsigned) r.n);      // one thread owns one element of one frame's sums
+  if (r.ev0) HIPCHK(hipEventRecord(r.ev0, r.stream));
+  hipLaunchKernelGGL(vvcx_alf_chroma_label_sum_kernel, grid, dim3(256), 0, r.stream, p);
+  HIPCHK(hipGetLastError());
+  if (r.ev0) HIPCHK(hipEventRecord(r.ev1, r.stream));
+  HIPCHK(hipMemcpyAsync(sums, w.lab_sum.p, ns * sizeof(long long), hipMemcpyDeviceToHost, r.stream));
+  HIPCHK(hipStreamSynchronize(r.stream));
+  if (r.ev0) HIPCHK(hipEventElapsedTime(&r.sum_ms, r.ev0, r.ev1));
+  r.calls++;
+  return VVCX_OK;
+}
+// per (frame, CTU, component) the cheapest of off and the frame's alternatives (vvcx_alf_chroma_assign_kernel), then the frames' costs (vvcx_alf_chroma_cost_kernel)
+int alf_assign(AlfRes &r, const vvcx_alf_chroma_cand *cands, int n_alts, const double lambda_c[2], uint8_t *labels, int64_t *err, double *cost)
+{
+  if (!r.chroma) return fail(VVCX_ERR_STATE, "ALF chroma alternatives: the statistics have no chroma");
+  if (!cands || !lambda_c || !labels || !err || !cost) return fail(VVCX_ERR_ARG, "null argument");
+  if (n_alts < 1 || n_alts > VX_ALF_MAX_ALTS) return fail(VVCX_ERR_ARG, "ALF chroma alternatives: %d (1..%d)", n_alts, VX_ALF_MAX_ALTS);
+  if (!(lambda_c[0] >= 0) || !(lambda_c[1] >= 0)) return fail(VVCX_ERR_ARG, "ALF chroma alternatives: lambdas");
+  for (size_t i = 0; i < (size_t) r.n * n_alts; i++) for (int k = 0; k < 6; k++)
+    if (cands[i].coeff[k] < -128 || cands[i].coeff[k] > 128 || cands[i].clip_idx[k] >= r.nb)
+      return fail(VVCX_ERR_ARG, "ALF chroma candidate %d: coefficient %d / clipping index %d (|q| <= 128, index < %d gathered bins)", (int) i, cands[i].coeff[k], cands[i].clip_idx[k], r.nb);
+  const size_t nlab = (size_t) r.n * r.nctu * 2;
+  AlfWork &w = *r.w;
+  HIPCHK(w.lab.reserve(nlab)); HIPCHK(w.alt_err.reserve(nlab)); HIPCHK(w.alt_term.reserve(nlab)); HIPCHK(w.alt_cost.reserve((size_t) r.n)); HIPCHK(w.cc.reserve((size_t) r.n * n_alts));
+  HIPCHK(hipMemcpyAsync(w.cc.p, cands, (size_t) r.n * n_alts * sizeof *cands, hipMemcpyHostToDevice, r.stream));
+  VxAlfAssignParams p; memset(&p, 0, sizeof p);
+  p.chroma = r.chroma; p.cands = w.cc.p; p.labels = w.lab.p; p.err = w.alt_err.p; p.term = w.alt_term.p; p.cost = w.alt_cost.p;
+  p.lambda_c[0] = lambda_c[0]; p.lambda_c[1] = lambda_c[1]; p.nctu = r.nctu; p.nb = r.nb; p.n_alts = n_alts;
+  const dim3 grid((unsigned) r.nctu, 2u, (unsigned) r.n);      // one workgroup owns one (CTU, component, frame)
+  if (r.ev0) HIPCHK(hipEventRecord(r.ev0, r.stream));
+  hipLaunchKernelGGL(vvcx_alf_chroma_assign_kernel, grid, dim3(256), 0, r.stream, p);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(vvcx_alf_chroma_cost_kernel, dim3((unsigned) r.n), dim3(64), 0, r.stream, p);
+  HIPCHK(hipGetLastError());
+  if (r.ev0) HIPCHK(hipEventRecord(r.ev1, r.stream));
+  HIPCHK(hipMemcpyAsync(labels, w.lab.p, nlab, hipMemcpyDeviceToHost, r.stream));
+  HIPCHK(hipMemcpyAsync(err, w.alt_err.p, nlab * sizeof(long long), hipMemcpyDeviceToHost, r.stream));
+  HIPCHK(hipMemcpyAsync(cost, w.alt_cost.p, (size_t) r.n * sizeof(double), hipMemcpyDeviceToHost, r.stream));
+  HIPCHK(hipStreamSynchronize(r.stream));
+  if (r.ev0) HIPCHK(hipEventElapsedTime(&r.cand_ms, r.ev0, r.ev1));
+  r.calls++;
+  return VVCX_OK;
+}
+
 static int alf_decide_args(const double lambda[3], int max_luma_filters, int flags, int nb)
 {
-  if (!lambda || max_luma_filters < 1 || max_luma_filters > 25 || !(lambda[0] >= 0) || !(lambda[1] >= 0) || !(lambda[2] >= 0) || flags < 0 || flags > 7)
+  if (!lambda || max_luma_filters < 1 || max_luma_filters > 25 || !(lambda[0] >= 0) || !(lambda[1] >= 0) || !(lambda[2] >= 0) || flags < 0 || (flags & 0xff) > 7 || (flags >> 8) > 7)
     return fail(VVCX_ERR_ARG, "ALF decision: filter count / lambdas / flags");
   if ((flags & (VVCX_ALF_NONLINEAR_LUMA | VVCX_ALF_NONLINEAR_CHROMA)) && nb != 4) return fail(VVCX_ERR_ARG, "ALF decision: nonlinear filters need statistics with 4 clipping bins");
   return VVCX_OK;
@@ -595,7 +655,7 @@ static int alf_resident(vvcx_handle *h, void *hip_stream, AlfRes &r)
 {
   if (!h->alf_res_valid) return fail(VVCX_ERR_STATE, "no resident ALF statistics (vvcx_alf_statistics_resident), or a call has touched the bound pictures since");
   r.luma = h->alf_stat_luma_d.p; r.chroma = h->alf_res_chroma ? h->alf_stat_chroma_d.p : nullptr; r.n = h->alf_res_n; r.nctu = h->ctus_w * h->ctus_h; r.nb = h->alf_res_bins;
-  r.w = &h->alf_work; r.stream = (hipStream_t) hip_stream; r.ev0 = h->ev0; r.ev1 = h->ev1; r.sum_ms = h->last_alf_sum_ms; r.cand_ms = h->last_alf_cand_ms;
+  r.w = &h->alf_work; r.stream = (hipStream_t) hip_stream; r.ev0 = h->ev0; r.ev1 = h->ev1; r.sum_ms = h->last_alf_sum_ms; r.cand_ms = h->last_alf_cand_ms; r.calls = 0;
   return VVCX_OK;
 }
 
@@ -632,9 +692,33 @@ extern "C" int vvcx_alf_decide_resident(vvcx_handle *h, const double lambda[3], 
   if (const int rc = alf_decide_args(lambda, max_luma_filters, flags, r.nb)) return rc;
   ON_DEVICE(h->cfg.device);
   const int rc = alf_decide_frames(r, r.chroma != nullptr, lambda, max_luma_filters, flags, aps, slices, ctus);
-  h->last_alf_sum_ms = r.sum_ms; h->last_alf_cand_ms = r.cand_ms;
+  h->last_alf_sum_ms = r.sum_ms; h->last_alf_cand_ms = r.cand_ms; h->last_alf_calls = r.calls;
   return rc;
 }
+extern "C" int vvcx_alf_chroma_label_sums(vvcx_handle *h, const uint8_t *labels, int n_alts, int64_t *sums, void *hip_stream)
+{
+  NOT_PENDING(h);
+  if (!h) return fail(VVCX_ERR_ARG, "null handle");
+  AlfRes r;
+  if (const int rc = alf_resident(h, hip_stream, r)) return rc;
+  ON_DEVICE(h->cfg.device);
+  const int rc = alf_label_sums(r, labels, n_alts, sums);
+  h->last_alf_sum_ms = r.sum_ms;
+  return rc;
+}
+extern "C" int vvcx_alf_chroma_assign(vvcx_handle *h, const vvcx_alf_chroma_cand *cands, int n_alts, const double lambda_c[2], uint8_t *labels, int64_t *err, double *cost,
+                                      void *hip_stream)
+{
+  NOT_PENDING(h);
+  if (!h) return fail(VVCX_ERR_ARG, "null handle");
+  AlfRes r;
+  if (const int rc = alf_resident(h, hip_stream, r)) return rc;
+  ON_DEVICE(h->cfg.device);
+  const int rc = alf_assign(r, cands, n_alts, lambda_c, labels, err, cost);
+  h->last_alf_cand_ms = r.cand_ms;
+  return rc;
+}
+extern "C" int vvcx_last_alf_device_calls(const vvcx_handle *h) { return h ? h->last_alf_calls : 0; }
 extern "C" float vvcx_last_alf_sum_ms(const vvcx_handle *h) { return h ? h->last_alf_sum_ms : 0.f; }
 extern "C" float vvcx_last_alf_cand_ms(const vvcx_handle *h) { return h ? h->last_alf_cand_ms : 0.f; }
 
@@ -652,6 +736,22 @@ extern "C" int vvcx_alf_evaluate_picture(int pic_w, int pic_h, int bit_depth, in
   r.luma = luma_d.p; r.chroma = chroma_d.p; r.n = 1; r.nctu = ((pic_w + 127) / 128) * ((pic_h + 127) / 128); r.nb = n_bins; r.w = &work;
   if (sums) if (const int rc = alf_sums(r, ctu_on, luma_sum, chroma_sum)) return rc;
   if (errs) if (const int rc = alf_errors(r, fixed_sets, luma_cands, n_luma, chroma_cands, n_chroma, luma_err, chroma_err)) return rc;
+  return VVCX_OK;
+}
+extern "C" int vvcx_alf_chroma_alts_picture(int pic_w, int pic_h, int bit_depth, int n_bins, const uint16_t *const org[3], const uint16_t *const rec[3], const uint8_t *labels_in,
+                                            const vvcx_alf_chroma_cand *cands, int n_alts, const double lambda_c[2], int64_t *sums, uint8_t *labels_out, int64_t *err, double *cost,
+                                            int device)
+{
+  if (const int rc = alf_picture_args("vvcx_alf_chroma_alts_picture", pic_w, pic_h, bit_depth, n_bins, org, rec)) return rc;
+  const bool want_sums = sums != nullptr, want_assign = labels_out || err || cost;
+  if (!want_sums && !want_assign) return fail(VVCX_ERR_ARG, "vvcx_alf_chroma_alts_picture: no output asked for");
+  ON_DEVICE(device);
+  DevBuf<long long> luma_d, chroma_d; AlfWork work;
+  if (const int rc = alf_stats_of_planes(pic_w, pic_h, bit_depth, n_bins, org, rec, true, luma_d, chroma_d)) return rc;
+  AlfRes r; memset(&r, 0, sizeof r);
+  r.luma = luma_d.p; r.chroma = chroma_d.p; r.n = 1; r.nctu = ((pic_w + 127) / 128) * ((pic_h + 127) / 128); r.nb = n_bins; r.w = &work;
+  if (want_sums) if (const int rc = alf_label_sums(r, labels_in, n_alts, sums)) return rc;
+  if (want_assign) if (const int rc = alf_assign(r, cands, n_alts, lambda_c, labels_out, err, cost)) return rc;
   return VVCX_OK;
 }
 extern "C" int vvcx_alf_decide_picture(int pic_w, int pic_h, int bit_depth, int n_bins, const uint16_t *const org[3], const uint16_t *const rec[3], const double lambda[3],

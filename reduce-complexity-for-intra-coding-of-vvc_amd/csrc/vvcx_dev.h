@@ -165,6 +165,27 @@ struct VxAlfCandParams {
   long long *chroma_err;          // [frame][ctu][2][n_chroma]
   int32_t nctu, nb, fixed_sets, n_luma, n_chroma, pad_;
 };
+// the two passes of the chroma-alternative iteration (vvcx_alf_eval.hip): the chroma blocks summed per label, and per (CTU, component) the cheapest of off and the
+// alternatives.  A label is 0 .. n_alts - 1 or VX_ALF_LABEL_OFF
+#define VX_ALF_MAX_ALTS  8
+#define VX_ALF_LABEL_OFF 255
+struct VxAlfLabelSumParams {
+  const long long *chroma;        // [frame][ctu][2][size_c]
+  const uint8_t *labels;          // [frame][ctu][2]
+  long long *out;                 // [frame][n_alts][size_c]
+  int32_t nctu, n_alts;
+  uint64_t size_c;
+};
+struct VxAlfAssignParams {
+  const long long *chroma;
+  const VxAlfChromaCand *cands;   // [frame][n_alts]
+  uint8_t *labels;                // [frame][ctu][2]
+  long long *err;                 // [frame][ctu][2]: the error of the chosen alternative, 0 when off
+  double *term;                   // [frame][ctu][2]: its cost (error / 16384 + lambda * bits), 0 when off
+  double *cost;                   // [frame]: the terms added in raster order, Cb before Cr (vvcx_alf_chroma_cost_kernel)
+  double lambda_c[2];
+  int32_t nctu, nb, n_alts, pad_;
+};
 
 // payload rewrite (vvcx_rewrite_kernel_*, vvcx_kernel.hip): every tile's slice_data once more from the stored CU maps and levels, with the SAO / ALF CTU syntax
 // (CABACWriter::coding_tree_unit, EL/CABACWriter.cpp:254-309) in front of each coding tree.  One workgroup per (frame, tile), thread 0 codes; no workgroup waits on another

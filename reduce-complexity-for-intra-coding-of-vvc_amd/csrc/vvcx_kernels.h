@@ -41,6 +41,9 @@ extern "C" __global__ void vvcx_alf_stats_b1_kernel_u16(VxAlfStatParams p);
 extern "C" __global__ void vvcx_alf_stats_b4_kernel_u16(VxAlfStatParams p);
 extern "C" __global__ void vvcx_alf_sum_kernel(VxAlfSumParams p);
 extern "C" __global__ void vvcx_alf_cand_kernel(VxAlfCandParams p);
+extern "C" __global__ void vvcx_alf_chroma_label_sum_kernel(VxAlfLabelSumParams p);
+extern "C" __global__ void vvcx_alf_chroma_assign_kernel(VxAlfAssignParams p);
+extern "C" __global__ void vvcx_alf_chroma_cost_kernel(VxAlfAssignParams p);
 extern "C" __global__ void vvcx_deblock_edges_kernel(VxDeblockParams p);
 extern "C" __global__ void vvcx_deblock_kernel_u8(VxDeblockParams p);
 extern "C" __global__ void vvcx_deblock_kernel_u16(VxDeblockParams p);

@@ -259,8 +259,14 @@ def alf_decide(luma, chroma, width, height, bit_depth, lambdas, n_bins=1, max_lu
 ALF_NONLINEAR_LUMA = 1       # flags of alf_decide_picture / VvcxEncoder.alf_decide_resident
 ALF_NONLINEAR_CHROMA = 2
 ALF_FIXED_SETS = 4
+ALF_LABEL_OFF = 255          # a (CTU, component) that no chroma alternative filters
 ALF_LUMA_CAND = np.dtype([("coeff", "<i2", (25, 12)), ("clip_idx", "u1", (25, 12))])      # vvcx_alf_luma_cand: per class, class_to_filter applied
 ALF_CHROMA_CAND = np.dtype([("coeff", "<i2", (6,)), ("clip_idx", "u1", (6,))])            # vvcx_alf_chroma_cand
+
+
+def ALF_CHROMA_ALTS(n):
+    """VVCX_ALF_CHROMA_ALTS: up to n (1..8) chroma alternatives, OR-ed into the flags of alf_decide_picture / VvcxEncoder.alf_decide_resident"""
+    return (int(n) - 1) << 8
 
 
 def alf_luma_cand(aps_row):
@@ -316,6 +322,38 @@ def alf_evaluate_picture(org, rec, bit_depth, n_bins=1, ctu_on=None, fixed_sets=
                                         cc.ctypes.data, cc.shape[1], sl.ctypes.data if want_sums else None, sc.ctypes.data if want_sums else None,
                                         el.ctypes.data if want_err else None, ec.ctypes.data if want_err else None, device))
     return (sl if want_sums else None, sc if want_sums else None, el if want_err else None, ec if want_err else None)
+
+
+def _alf_alts_args(labels, cands, n_alts, n, nctu):
+    """labels as uint8 [frames, ctus, 2], candidates as ALF_CHROMA_CAND [frames, n_alts] (a flat list belongs to n frames), n_alts (None: as many as there are
+    candidates, else the largest label + 1)"""
+    lab = None if labels is None else np.ascontiguousarray(labels, np.uint8).reshape(-1, nctu, 2)
+    cc = None if cands is None else np.ascontiguousarray(cands, ALF_CHROMA_CAND)
+    if cc is not None and cc.ndim != 2:
+        cc = cc.reshape(n, -1)
+    if n_alts is None:
+        n_alts = cc.shape[1] if cc is not None else 0 if lab is None else int(lab[lab != ALF_LABEL_OFF].max(initial=0)) + 1
+    return lab, cc, int(n_alts)
+
+
+def alf_chroma_alts_picture(org, rec, bit_depth, n_bins=1, labels=None, cands=None, n_alts=None, lambda_c=(0.0, 0.0), device=0, lib_path=None):
+    """vvcx_alf_chroma_alts_picture: the two passes of the chroma-alternative iteration on one picture in host memory.  labels uint8 [ctus, 2] (an alternative or
+    ALF_LABEL_OFF) -> sums int64 [n_alts, .] of the Cb + Cr blocks per label; cands ALF_CHROMA_CAND [n_alts], lambda_c (Cb, Cr) -> labels uint8 [ctus, 2], err int64
+    [ctus, 2], cost float.  Returns (sums, labels, err, cost); the half that was not asked for is None.  n_alts: taken from cands / labels when None"""
+    L = load_library(lib_path)
+    o = [np.ascontiguousarray(p.astype(np.uint16)) for p in org]; r = [np.ascontiguousarray(p.astype(np.uint16)) for p in rec]
+    h, w = r[0].shape
+    nctu = ((w + 127) // 128) * ((h + 127) // 128)
+    _, szc = alf_stat_sizes(n_bins if n_bins in (1, 4) else 1)
+    lab, cc, n_alts = _alf_alts_args(labels, cands, n_alts, 1, nctu)
+    lam = np.ascontiguousarray(lambda_c, np.float64)
+    sums = np.zeros((max(n_alts, 1), szc), np.int64); lo = np.zeros((nctu, 2), np.uint8); err = np.zeros((nctu, 2), np.int64); cost = np.zeros(1, np.float64)
+    op = (C.c_void_p * 3)(*[p.ctypes.data for p in o]); rp = (C.c_void_p * 3)(*[p.ctypes.data for p in r])
+    L.vvcx_alf_chroma_alts_picture.argtypes = [C.c_int] * 4 + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 5 + [C.c_int]
+    _chk(L, L.vvcx_alf_chroma_alts_picture(w, h, bit_depth, n_bins, op, rp, None if lab is None else lab.ctypes.data, None if cc is None else cc.ctypes.data, n_alts,
+                                           lam.ctypes.data, None if lab is None else sums.ctypes.data, *([None] * 3 if cc is None else [lo.ctypes.data, err.ctypes.data, cost.ctypes.data]),
+                                           device))
+    return (None if lab is None else sums[:n_alts],) + ((None, None, None) if cc is None else (lo, err, float(cost[0])))
 
 
 def alf_decide_picture(org, rec, bit_depth, lambdas, n_bins=1, max_luma_filters=25, flags=0, device=0, lib_path=None):
@@ -528,6 +566,32 @@ class VvcxEncoder:
         self.L.vvcx_alf_candidate_errors.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         self._chk(self.L.vvcx_alf_candidate_errors(self.h, int(bool(fixed_sets)), lc.ctypes.data, lc.shape[1], cc.ctypes.data, cc.shape[1], el.ctypes.data, ec.ctypes.data, None))
         return el, ec
+
+    def alf_chroma_label_sums(self, labels, n_alts=None):
+        """vvcx_alf_chroma_label_sums: labels uint8 [n, ctus, 2] (an alternative or ALF_LABEL_OFF) -> int64 [n, n_alts, .]: the resident Cb + Cr blocks summed per label"""
+        n, nb, _, szc = self._alf_resident_shape()
+        lab, _, n_alts = _alf_alts_args(labels, None, n_alts, n, self.ctus_per_frame)
+        sums = np.zeros((max(n, lab.shape[0]), max(n_alts, 1), szc), np.int64)
+        self.L.vvcx_alf_chroma_label_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        self._chk(self.L.vvcx_alf_chroma_label_sums(self.h, lab.ctypes.data, n_alts, sums.ctypes.data, None))
+        return sums[:, :n_alts]
+
+    def alf_chroma_assign(self, cands, lambda_c, n_alts=None):
+        """vvcx_alf_chroma_assign: cands ALF_CHROMA_CAND [n, n_alts], lambda_c (Cb, Cr) -> (labels uint8 [n, ctus, 2], err int64 [n, ctus, 2], cost float64 [n]): per
+        (CTU, component) the cheapest of off and the frame's alternatives"""
+        n, nb, _, _ = self._alf_resident_shape()
+        _, cc, n_alts = _alf_alts_args(None, cands, n_alts, n, self.ctus_per_frame)
+        lam = np.ascontiguousarray(lambda_c, np.float64)
+        n = max(n, cc.shape[0])
+        lab = np.zeros((n, self.ctus_per_frame, 2), np.uint8); err = np.zeros((n, self.ctus_per_frame, 2), np.int64); cost = np.zeros(n, np.float64)
+        self.L.vvcx_alf_chroma_assign.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        self._chk(self.L.vvcx_alf_chroma_assign(self.h, cc.ctypes.data, n_alts, lam.ctypes.data, lab.ctypes.data, err.ctypes.data, cost.ctypes.data, None))
+        return lab, err, cost
+
+    def alf_device_calls(self):
+        """vvcx_last_alf_device_calls: the blocking device passes of the last alf_decide_resident"""
+        self.L.vvcx_last_alf_device_calls.restype = C.c_int; self.L.vvcx_last_alf_device_calls.argtypes = [C.c_void_p]
+        return int(self.L.vvcx_last_alf_device_calls(self.h))
 
     def alf_decide_resident(self, lambdas, max_luma_filters=25, flags=0):
         """vvcx_alf_decide_resident: the decision of every resident frame -> one dict of alf_decide's form per frame (each with its own parameter set as aps[0])"""

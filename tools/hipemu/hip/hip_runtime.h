@@ -116,6 +116,9 @@ inline int __clzll(long long v) { return v == 0 ? 64 : __builtin_clzll((unsigned
 inline int __popcll(unsigned long long v) { return __builtin_popcountll(v); }
 inline int __ffsll(unsigned long long v) { return __builtin_ffsll((long long) v); }
 inline int __clz(int v) { return v == 0 ? 32 : __builtin_clz((unsigned) v); }
+// separately rounded double operations (the emulator is built with -ffp-contract=off; the volatile keeps the two apart whatever the flags)
+inline double __dmul_rn(double a, double b) { volatile double r = a * b; return r; }
+inline double __dadd_rn(double a, double b) { volatile double r = a + b; return r; }
 inline unsigned long long atomicAdd(unsigned long long *p, unsigned long long v) { const unsigned long long o = *p; *p += v; return o; }
 inline unsigned atomicAdd(unsigned *p, unsigned v) { const unsigned o = *p; *p += v; return o; }
 inline int atomicAdd(int *p, int v) { const int o = *p; *p += v; return o; }
